@@ -1,17 +1,28 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X-native SereneDB hot path.
 
-Default workload = "all": the FULL BASELINE metric ("docs scored/sec BM25
-top-1000 (+ rows/sec filter-agg)") — the primary line is configs[1] (BM25
-top-1000, 4-term disjunction, 100M synthetic docs, seed 43, SURVEY.md §8d
-distributions) and the same JSON line embeds the configs[2] scan
-(1B-row scan->filter->group-by, seed 44) and configs[3] hybrid results
-under "extra_benches", each with its own roofline and cpu_baseline (the
-round-1 driver record certified only the BM25 half — VERDICT #4).
+Default workload = "all": the primary line is configs[1] (BM25 top-1000,
+4-term disjunction, 100M synthetic docs, seed 43, SURVEY.md §8d
+distributions). A plain run does only what that headline needs: build and
+load the segment, warm up, time --steps queries, print the line.
+
+With --full the same JSON line is the FULL BASELINE metric ("docs
+scored/sec BM25 top-1000 (+ rows/sec filter-agg)"): it also embeds the
+configs[2] scan (1B-row scan->filter->group-by, seed 44) and configs[3]
+hybrid results under "extra_benches", each with its own roofline and
+cpu_baseline (the round-1 driver record certified only the BM25 half —
+VERDICT #4), and re-asserts that the pipelined batch entry returns what
+the per-step entry does.
 A "step" is one full query execution (decode -> score -> top-k -> merge),
 resp. one full scan->filter->group-by pass.
 
   python bench.py --gpus N --steps K --warmup W [--workload bm25_topk]
+                  [--full] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step returned to its caller
+as DIR/<workload>_<name>.npy (float32 scores; doc ids, match totals and
+aggregate slots as float64, exact below 2^53). Inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
 
 For N>1 the driver launches this under torch.distributed.run (one rank per
 GPU over RCCL); ranks shard the SAME corpus by doc range (strong scaling,
@@ -183,16 +194,19 @@ def bench_bm25(args, dist, hybrid=False):
     lib = sa.gpu()
     lib.sdb_gpu_last_kernel_ms.restype = CT.c_int
 
+    last_buckets = [None]  # hybrid: merged [bcnt | bsum] of the last step
+
     def step():
         if hybrid:
             hits, total, bcnt, bsum = ctx.execute_topk_hybrid(
                 [seg], term_idx, boosts, k, flo, fhi, nbuckets,
                 global_stats=gstats)
+            last_buckets[0] = np.concatenate([bcnt, bsum])
             if dist:
                 import torch
-                bb = torch.from_numpy(np.concatenate([bcnt, bsum])).cuda()
+                bb = torch.from_numpy(last_buckets[0]).cuda()
                 dist.all_reduce(bb)  # partial-agg merge
-                _ = bb.cpu().numpy()
+                last_buckets[0] = bb.cpu().numpy()
         else:
             hits, total = ctx.execute_topk([seg], term_idx, boosts, k,
                                            global_stats=gstats)
@@ -230,26 +244,32 @@ def bench_bm25(args, dist, hybrid=False):
     # production QPS shape. Kernel-trace cadence 0.49 ms/query vs 0.67
     # per-step at 100M (profiles/r2_evidence/r2_batch_trace.log); results
     # bit-equal per query (tests/test_gpu_parity.py
-    # test_batch_pipelined_equals_single, re-asserted in warmup here).
-    # Hybrid keeps per-step (the batch entry carries no bucket state).
+    # test_batch_pipelined_equals_single; --full re-asserts it here
+    # against the per-step entry). The 2-query batch always runs: it is
+    # the warmup of the batch entry itself (the loop above warms per-step).
     use_batch = args.execution == "batch"
     if use_batch and not hybrid:
-        ref_hits, ref_total = ctx.execute_topk([seg], term_idx, boosts, k,
-                                               global_stats=gstats)
+        if args.full:
+            ref_hits, ref_total = ctx.execute_topk(
+                [seg], term_idx, boosts, k, global_stats=gstats)
         bh, bt = ctx.execute_topk_batch([seg], term_idx, boosts, k, 2,
                                         global_stats=gstats, all_hits=True)
-        assert bt[0] == ref_total and len(bh[0]) == len(ref_hits)
-        assert all(tuple(a) == tuple(b) for a, b in zip(bh[0], ref_hits))
+        if args.full:
+            assert bt[0] == ref_total and len(bh[0]) == len(ref_hits)
+            assert all(tuple(a) == tuple(b)
+                       for a, b in zip(bh[0], ref_hits))
     elif use_batch:
-        rh, rt, rc_, rs = ctx.execute_topk_hybrid(
-            [seg], term_idx, boosts, k, flo, fhi, nbuckets,
-            global_stats=gstats)
+        if args.full:
+            rh, rt, rc_, rs = ctx.execute_topk_hybrid(
+                [seg], term_idx, boosts, k, flo, fhi, nbuckets,
+                global_stats=gstats)
         bh, bt, bc, bs = ctx.execute_topk_hybrid_batch(
             [seg], term_idx, boosts, k, flo, fhi, nbuckets, 2,
             global_stats=gstats, all_hits=True)
-        assert bt[0] == rt and len(bh[0]) == len(rh)
-        assert all(tuple(a) == tuple(b) for a, b in zip(bh[0], rh))
-        assert (bc[0] == rc_).all() and (bs[0] == rs).all()
+        if args.full:
+            assert bt[0] == rt and len(bh[0]) == len(rh)
+            assert all(tuple(a) == tuple(b) for a, b in zip(bh[0], rh))
+            assert (bc[0] == rc_).all() and (bs[0] == rs).all()
     kernel_ms_acc = 0.0
     sync()
     t0 = time.time()
@@ -281,7 +301,7 @@ def bench_bm25(args, dist, hybrid=False):
                     bb = torch.from_numpy(
                         np.concatenate([bc[q], bs[q]])).cuda()
                     dist.all_reduce(bb)  # partial-agg merge
-                    _ = bb.cpu().numpy()
+                    last_buckets[0] = bb.cpu().numpy()
     else:
         for _ in range(args.steps):
             scores, docs, total = step()
@@ -295,6 +315,24 @@ def bench_bm25(args, dist, hybrid=False):
         te = torch.tensor([elapsed], device="cuda")
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
+
+    # ---- what the last timed step handed its caller (--dump-outputs) ----
+    if use_batch and dist:
+        allp = torch.cat(gathered).cpu().numpy()
+        allp.sort()
+        scores, docs = unpack_hits(allp[::-1][:k])
+    elif use_batch:
+        scores, docs = hits_l["score"], hits_l["doc"]
+        if hybrid:
+            last_buckets[0] = np.concatenate([bc[-1], bs[-1]])
+    outputs = {
+        "scores": np.asarray(scores, dtype=np.float32),
+        "docs": np.asarray(docs, dtype=np.float64),
+        "total_matches": np.array([total], dtype=np.float64),
+    }
+    if hybrid:
+        outputs["bucket_count"] = last_buckets[0][:nbuckets].astype(np.float64)
+        outputs["bucket_sum"] = last_buckets[0][nbuckets:].astype(np.float64)
 
     ms_per_step = elapsed * 1000.0 / args.steps
     # BASELINE's metric is DOCS scored/sec: every matched doc is scored
@@ -327,10 +365,11 @@ def bench_bm25(args, dist, hybrid=False):
                    if traffic else ""),
     }
 
-    # ---- CPU baseline (rank 0, N=1 only): the oracle's multithreaded
-    # mechanics path (RunTopKScan restatement) on a bounded sample ----
+    # ---- CPU baseline (--full; rank 0, N=1 only): the oracle's
+    # multithreaded mechanics path (RunTopKScan restatement) on a bounded
+    # sample ----
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import pyoracle as po
 
         # the full corpus IS the sample at N=1 (most honest: identical
@@ -421,7 +460,7 @@ def bench_bm25(args, dist, hybrid=False):
         "cpu_baseline": cpu_baseline,
     }
     ctx.close()
-    return result
+    return result, outputs
 
 
 def bench_scan(args, dist):
@@ -487,6 +526,7 @@ def bench_scan(args, dist):
     aggs = (AggSpec * 3)(AggSpec(0, 0), AggSpec(1, 1), AggSpec(2, 2))
     out = (AggResult * (ngroups * 3))()
     passed = CT.c_uint64(0)
+    merged = [None, None]  # N>1: allreduced (i64, f64) slots of the last step
 
     def step():
         rc = lib.sdb_gpu_scan_agg(ctx._ctx, tab, 0, ngroups, preds, 1, aggs,
@@ -504,8 +544,7 @@ def bench_scan(args, dist):
             tf = torch.from_numpy(farr).cuda()
             dist.all_reduce(t)
             dist.all_reduce(tf)
-            _ = t.cpu().numpy()
-            _ = tf.cpu().numpy()
+            merged[:] = t.cpu().numpy(), tf.cpu().numpy()
 
     def sync():
         if dist:
@@ -529,6 +568,23 @@ def bench_scan(args, dist):
     ms_per_step = elapsed * 1000 / args.steps
     value = rows_total * args.steps / elapsed
 
+    # ---- what the last timed step handed its caller (--dump-outputs):
+    # per group COUNT, SUM(i64), SUM(f32->f64); rows_passed is this
+    # rank's (the step merges only the group slots) ----
+    if dist:
+        i64s, f64s = merged
+    else:
+        i64s = np.array([out[i].i64 for i in range(ngroups * 3)],
+                        dtype=np.int64)
+        f64s = np.array([out[i].f64 for i in range(ngroups * 3)],
+                        dtype=np.float64)
+    outputs = {
+        "count": i64s[0::3].astype(np.float64),
+        "sum_i64": i64s[1::3].astype(np.float64),
+        "sum_f64": f64s[2::3].astype(np.float64),
+        "rows_passed": np.array([passed.value], dtype=np.float64),
+    }
+
     algo_bytes = scan_bytes  # compressed (FoR) or raw column bytes scanned
     achieved_gbs = algo_bytes * args.steps / elapsed / 1e9  # whole step ~ kernel
     scan_wl_key = (f"scan_filter_groupby_{rows_total//10**9}B"
@@ -536,7 +592,7 @@ def bench_scan(args, dist):
                    else f"scan_filter_groupby_{rows_total}")
     scan_traffic, scan_traffic_note = pmc_traffic(scan_wl_key)
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import pyoracle as po
 
         ncores = os.cpu_count() or 1
@@ -596,7 +652,17 @@ def bench_scan(args, dist):
     }
     lib.sdb_gpu_table_free(ctx._ctx, tab)
     ctx.close()
-    return result
+    return result, outputs
+
+
+def dump_outputs(out_dir, named):
+    """--dump-outputs: one <name>.npy per array, float32/float64 only."""
+    os.makedirs(out_dir, exist_ok=True)
+    nbytes = sum(a.nbytes for a in named.values())
+    assert nbytes <= 64 << 20, nbytes  # top-k hits + group slots: ~100 KB
+    for name, arr in named.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def main():
@@ -611,26 +677,51 @@ def main():
     ap.add_argument("--scan-codec", default="raw", choices=["for", "raw"])
     ap.add_argument("--execution", default="batch", choices=["batch", "step"])
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the "
+                         "CPU baselines, the batch-vs-per-step check and, "
+                         "for --workload all, the scan and hybrid benches")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's results to "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     rank, world = env_rank()
     dist = dist_init(world)
 
+    dumps = {}
+
+    def keep(prefix, outputs):
+        dumps.update((f"{prefix}_{n}", a) for n, a in outputs.items())
+
     if args.workload == "bm25_topk":
-        primary = bench_bm25(args, dist, hybrid=False)
+        primary, outs = bench_bm25(args, dist, hybrid=False)
+        keep("bm25", outs)
     elif args.workload == "hybrid":
-        primary = bench_bm25(args, dist, hybrid=True)
+        primary, outs = bench_bm25(args, dist, hybrid=True)
+        keep("hybrid", outs)
     elif args.workload == "scan_agg":
-        primary = bench_scan(args, dist)
+        primary, outs = bench_scan(args, dist)
+        keep("scan", outs)
     else:
-        # the full BASELINE metric: BM25 primary + scan and hybrid
-        # embedded, every half driver-certified in one record
-        primary = bench_bm25(args, dist, hybrid=False)
-        scan = bench_scan(args, dist)
-        hyb = bench_bm25(args, dist, hybrid=True)
+        # the headline: BM25 top-1000. --full embeds the scan and hybrid
+        # benches too (the full BASELINE metric, every half certified in
+        # one record)
+        primary, outs = bench_bm25(args, dist, hybrid=False)
+        keep("bm25", outs)
         primary["metric"] = \
             "docs scored/sec BM25 top-1000 (+ rows/sec filter-agg)"
-        primary["extra_benches"] = [scan, hyb]
+        if args.full:
+            scan, outs = bench_scan(args, dist)
+            keep("scan", outs)
+            hyb, outs = bench_bm25(args, dist, hybrid=True)
+            keep("hybrid", outs)
+            primary["extra_benches"] = [scan, hyb]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dumps)
     if rank == 0:
         print(json.dumps(primary), flush=True)
     if dist:

@@ -42,6 +42,24 @@ def test_pack_sort_order_matches_engine_order():
     np.testing.assert_array_equal(d2, [9, 3, 17, 50, 1])
 
 
+def test_dump_outputs_writes_float_npy_only(tmp_path):
+    import pytest
+
+    d = str(tmp_path / "out" / "nested")
+    arrs = {"bm25_scores": np.array([2.5, 1.0], dtype=np.float32),
+            "bm25_docs": np.array([7, 4_000_000_000], dtype=np.float64)}
+    bench.dump_outputs(d, arrs)
+    assert sorted(os.listdir(d)) == ["bm25_docs.npy", "bm25_scores.npy"]
+    for name, a in arrs.items():
+        b = np.load(os.path.join(d, name + ".npy"))
+        assert b.dtype == a.dtype
+        np.testing.assert_array_equal(a, b)
+    with pytest.raises(AssertionError):  # integer arrays are never dumped
+        bench.dump_outputs(d, {"x": np.zeros(2, dtype=np.int64)})
+    with pytest.raises(AssertionError):  # 64 MB ceiling
+        bench.dump_outputs(d, {"x": np.zeros((64 << 17) + 1)})
+
+
 def test_pack_base_offset_and_padding():
     # sharded ranks add their doc base; k > len(hits) pads with minimal
     # keys that sort below every real hit
