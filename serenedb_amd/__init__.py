@@ -717,9 +717,21 @@ class GpuContext:
     class _AggResult(C.Structure):
         _fields_ = [("i64", C.c_int64), ("f64", C.c_double)]
 
-    def load_table(self, arrays, codecs=None):
+    @staticmethod
+    def _unpack_aggs(out, n, na):
+        """First n*na SdbAggResult slots of `out` as ([n, na] int64,
+        [n, na] float64), in one copy each (a per-slot ctypes read costs
+        more than the scan itself on small tables)."""
+        import numpy as np
+
+        dt = np.dtype([("i64", "<i8"), ("f64", "<f8")])
+        rec = np.frombuffer(out, dtype=dt, count=n * na).reshape(n, na)
+        return rec["i64"].copy(), rec["f64"].copy()
+
+    def load_table(self, arrays, codecs=None, group_rows=65536):
         """arrays: list of numpy arrays (int64 or float32). codecs: per
-        column, "raw" or "for" (i64 only). Returns an opaque table handle.
+        column, "raw" or "for" (i64 only); group_rows: the row-group tiling
+        of every "for" column. Returns an opaque table handle.
         Keeps the encoded blobs alive for the duration of the call only
         (table_load uploads them)."""
         import numpy as np
@@ -736,7 +748,8 @@ class GpuContext:
                 views[i] = self._ColView(
                     a.ctypes.data_as(C.c_void_p).value, rows, 1)
             elif enc == "for":
-                blob = encode_col_i64(np.ascontiguousarray(a, np.int64))
+                blob = encode_col_i64(np.ascontiguousarray(a, np.int64),
+                                      group_rows)
                 bv = np.frombuffer(blob, dtype=np.uint8)
                 keep.append(bv)
                 views[i] = self._ColView(
@@ -859,10 +872,7 @@ class GpuContext:
             C.c_uint32(np_), aa, C.c_uint32(na), out, C.byref(passed))
         if rc != 0:
             raise RuntimeError(f"sdb_gpu_scan_agg rc={rc}")
-        i64 = np.array([[out[g * na + q].i64 for q in range(na)]
-                        for g in range(ngroups)], dtype=np.int64)
-        f64 = np.array([[out[g * na + q].f64 for q in range(na)]
-                        for g in range(ngroups)], dtype=np.float64)
+        i64, f64 = self._unpack_aggs(out, ngroups, na)
         return i64, f64, passed.value
 
     def scan_agg_hash_str(self, tab, str_slot, max_groups, preds, aggs,
@@ -949,12 +959,8 @@ class GpuContext:
         if rc != 0:
             raise RuntimeError(f"sdb_gpu_scan_agg_hash rc={rc}")
         n = ng.value
-        i64 = np.array([[out[g * na + q].i64 for q in range(na)]
-                        for g in range(n)], dtype=np.int64)
-        f64 = np.array([[out[g * na + q].f64 for q in range(na)]
-                        for g in range(n)], dtype=np.float64)
-        return keys_out[:n], i64.reshape(n, na), f64.reshape(n, na), \
-            passed.value
+        i64, f64 = self._unpack_aggs(out, n, na)
+        return keys_out[:n], i64, f64, passed.value
 
 
     def execute_topk_batch(self, segs, term_idx, boosts, k, nq,
