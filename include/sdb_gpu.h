@@ -334,7 +334,11 @@ int sdb_gpu_strpred_mask(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t slot,
  * 254, total symbol bytes <= 2048); code 255 escapes the next literal
  * byte. offsets[rows+1] index the ENCODED blob. Predicates on such a
  * slot (same sdb_gpu_strpred_mask call) decode on the fly against the
- * plain-byte literal — semantics identical to the uncompressed slot. */
+ * plain-byte literal — semantics identical to the uncompressed slot.
+ * A malformed row (a code >= nsym, or an escape as its last byte) is
+ * detected before any read past it: it matches no predicate at all,
+ * PREFIX "" and GE "" included, and in sdb_gpu_scan_agg_hash_str all such
+ * rows form one group whose key is 0x8000000000000001. */
 int sdb_gpu_table_attach_strcol_fsst(SdbGpuCtx* ctx, SdbGpuTable* tab,
                                      uint32_t slot,
                                      const uint64_t* offsets,

@@ -1958,7 +1958,8 @@ struct StrHashArgs {
   const uint8_t* blob;
   uint64_t rows;
   long long* out;
-  uint32_t nsym;  // 0 = raw slot
+  uint32_t fsst;  // 0 = raw slot; an FSST slot may have nsym == 0
+  uint32_t nsym;
   uint16_t symoff[256];
   uint8_t syms[2048];
 };
@@ -1977,7 +1978,7 @@ __global__ void strhash_kernel(StrHashArgs ha) {
     const uint64_t o0 = ha.off[r], o1 = ha.off[r + 1];
     unsigned long long h = 14695981039346656037ull;
     bool bad = false;
-    if (ha.nsym == 0) {  // raw bytes
+    if (!ha.fsst) {  // raw bytes
       for (uint64_t i = o0; i < o1; ++i) {
         h ^= ha.blob[i];
         h *= 1099511628211ull;
@@ -2031,6 +2032,7 @@ int sdb_gpu_scan_agg_hash_str(SdbGpuCtx* ctx, SdbGpuTable* tab,
   ha.rows = tab->rows;
   ha.out = d_hash;
   if (tab->str_fsst[str_slot]) {
+    ha.fsst = 1;
     ha.nsym = tab->str_nsym[str_slot];
     std::memcpy(ha.symoff, tab->str_symoff[str_slot], sizeof(ha.symoff));
     std::memcpy(ha.syms, tab->str_syms[str_slot], sizeof(ha.syms));

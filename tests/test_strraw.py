@@ -260,8 +260,9 @@ def test_str_groupby_hash_parity():
                for i, k in enumerate(ks)}
         assert got == exp, f"slot {slot}"
         # result order: signed-i64 ascending on the hash
-        hs = [np.int64(np.uint64(fnv1a64(k))) for k in got]
-        assert sorted(hs) == sorted(hs)
+        hs = [int(np.uint64(fnv1a64(bytes(k))).astype(np.int64)) for k in ks]
+        assert hs == sorted(hs), f"slot {slot}"
+        assert hs[0] < 0 < hs[-1]
 
     # with a string predicate (prefix) AND a numeric predicate
     ctx.strpred_mask(tab, 0, "prefix", "c", None)
