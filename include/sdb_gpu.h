@@ -355,10 +355,43 @@ typedef struct SdbPredSpec {
   float flo, fhi;
 } SdbPredSpec;
 
+/* Aggregates. Every op but COUNT(*) reads column `col` and skips NULL
+ * values (a cleared validity bit), as SUM always has.
+ *
+ * COUNT_COL takes a column of any type (I64, I64_FOR or F32) and counts
+ * the passing rows whose value is not NULL; with no validity plane
+ * attached it equals COUNT(*).
+ *
+ * MIN_I64 / MAX_I64 take an i64 or FoR column, MIN_F32 / MAX_F32 an f32
+ * column. The f32 order is bitwise deterministic whatever order the
+ * device atomics run in: every NaN is first canonicalised to the positive
+ * quiet NaN 0x7FC00000 (so a NaN with the sign bit set lands at the top,
+ * not the bottom), then values compare in IEEE total order
+ *   -inf < ... < -0.0 < +0.0 < ... < +inf < NaN.
+ * MAX is NaN as soon as one non-NULL NaN passes; MIN is NaN only if every
+ * non-NULL passing value is NaN — the "NaN is the greatest value" rule of
+ * the DuckDB consumer being replaced; -0.0 < +0.0 is a deterministic
+ * refinement of it.
+ *
+ * A group with no non-NULL passing value (an empty group of the dense
+ * scan, or one whose passing rows are all NULL in `col`) returns the op's
+ * identity: MIN_I64 INT64_MAX, MAX_I64 INT64_MIN, MIN_F32 +inf, MAX_F32
+ * -inf. SQL's NULL result is "COUNT_COL of the same column is 0": ask for
+ * it alongside when the distinction matters.
+ *
+ * An op outside this enum, a column index >= ncols (for any op but
+ * COUNT(*)), SUM_I64 / MIN_I64 / MAX_I64 on an f32 column and SUM_F64 /
+ * MIN_F32 / MAX_F32 on a non-f32 column return SDB_ERR_INVALID before
+ * anything is launched. */
 typedef enum SdbAggOp {
   SDB_AGG_COUNT = 0,
   SDB_AGG_SUM_I64 = 1, /* exact wrap-around i64 sum */
   SDB_AGG_SUM_F64 = 2, /* f32 column summed in f64 */
+  SDB_AGG_COUNT_COL = 3, /* COUNT(col): passing rows whose value is not NULL */
+  SDB_AGG_MIN_I64 = 4,   /* i64 / FoR column */
+  SDB_AGG_MAX_I64 = 5,
+  SDB_AGG_MIN_F32 = 6,   /* f32 column */
+  SDB_AGG_MAX_F32 = 7,
 } SdbAggOp;
 
 typedef struct SdbAggSpec {
@@ -367,8 +400,11 @@ typedef struct SdbAggSpec {
 } SdbAggSpec;
 
 /* group_key column must be i64 with values in [0, ngroups).
- * out layout: for each group g, naggs consecutive values; COUNT/SUM_I64
- * results are int64 stored in the i64 field, SUM_F64 in the f64 field. */
+ * out layout: for each group g, naggs consecutive values. COUNT, SUM_I64,
+ * COUNT_COL, MIN_I64 and MAX_I64 results are int64 stored in the i64 field
+ * (f64 = 0); SUM_F64, MIN_F32 and MAX_F32 results are stored in the f64
+ * field (i64 = 0) — for MIN/MAX the winning f32 widened to double, exact,
+ * sign of zero preserved. */
 typedef struct SdbAggResult {
   int64_t i64;
   double f64;

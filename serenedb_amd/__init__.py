@@ -848,12 +848,32 @@ class GpuContext:
         if rc != 0:
             raise RuntimeError(f"strpred_mask rc={rc}")
 
+    # SdbAggOp (include/sdb_gpu.h) by name; every (col, op) aggregate pair
+    # takes the name or the number
+    AGG_OPS = {"count": 0, "sum_i64": 1, "sum_f64": 2, "count_col": 3,
+               "min_i64": 4, "max_i64": 5, "min_f32": 6, "max_f32": 7}
+
+    def _agg_specs(self, aggs):
+        """[(col, op)] -> SdbAggSpec array; op an AGG_OPS name or the
+        numeric SdbAggOp (passed through unchecked: the C entry rejects an
+        unknown one)."""
+        return (self._AggSpec * len(aggs))(*[
+            self._AggSpec(c, self.AGG_OPS[o] if isinstance(o, str)
+                          else int(o)) for c, o in aggs])
+
     def scan_agg(self, tab, group_col, ngroups, preds, aggs):
         """preds: list of (col, op, lo, hi) with SdbPredOp numeric op
         (1=LT 2=GE 3=BETWEEN 4=EQ); lo/hi int or float (float for f32
-        predicate columns). aggs: list of (col, op) with 0=COUNT
-        1=SUM_I64 2=SUM_F64. Returns (i64 results [ngroups, naggs],
-        f64 results [ngroups, naggs], rows_passed)."""
+        predicate columns). aggs: list of (col, op), op a name of AGG_OPS
+        or its number: 0=COUNT 1=SUM_I64 2=SUM_F64 3=COUNT_COL 4=MIN_I64
+        5=MAX_I64 6=MIN_F32 7=MAX_F32. Returns (i64 results [ngroups,
+        naggs], f64 results [ngroups, naggs], rows_passed): COUNT, SUM_I64,
+        COUNT_COL, MIN_I64 and MAX_I64 land in the i64 array, SUM_F64,
+        MIN_F32 and MAX_F32 in the f64 array (the other array holds 0).
+        Every column aggregate skips NULLs. f32 MIN/MAX order values as
+        -inf < ... < -0.0 < +0.0 < ... < +inf < NaN (any NaN); a group with
+        no non-NULL passing value returns the identity (INT64_MAX /
+        INT64_MIN / +inf / -inf) and COUNT_COL 0."""
         import numpy as np
 
         np_ = len(preds)
@@ -864,7 +884,7 @@ class GpuContext:
             else:
                 pa[i] = self._PredSpec(col, op, lo, hi, 0, 0)
         na = len(aggs)
-        aa = (self._AggSpec * na)(*[self._AggSpec(c, o) for c, o in aggs])
+        aa = self._agg_specs(aggs)
         out = (self._AggResult * (ngroups * na))()
         passed = C.c_uint64(0)
         rc = self._lib.sdb_gpu_scan_agg(
@@ -878,6 +898,7 @@ class GpuContext:
     def scan_agg_hash_str(self, tab, str_slot, max_groups, preds, aggs,
                           values=None):
         """GROUP BY string keys over an attached raw/FSST string slot.
+        aggs as in scan_agg (AGG_OPS names or numbers).
         Returns (keys, i64 [n, naggs], f64 [n, naggs], rows_passed):
         keys are the FNV-1a 64 group hashes (signed-i64 ascending), or —
         when `values` (the column's strings) is given — the resolved
@@ -894,7 +915,7 @@ class GpuContext:
             else:
                 pa[i] = self._PredSpec(col, op, lo, hi, 0, 0)
         na = len(aggs)
-        aa = (self._AggSpec * na)(*[self._AggSpec(c, o) for c, o in aggs])
+        aa = self._agg_specs(aggs)
         keys = np.zeros(max_groups, dtype=np.int64)
         out = (self._AggResult * (max_groups * na))()
         ng = C.c_uint64(0)
@@ -933,9 +954,10 @@ class GpuContext:
                              [(0, 0), (1, 1)])
 
     def scan_agg_hash(self, tab, group_col, max_groups, preds, aggs):
-        """General hash aggregate (arbitrary i64 keys). Returns
-        (keys[n], i64 results [n, naggs], f64 results [n, naggs],
-        rows_passed), rows sorted by key ascending."""
+        """General hash aggregate (arbitrary i64 keys); aggs as in
+        scan_agg (AGG_OPS names or numbers). Returns (keys[n], i64 results
+        [n, naggs], f64 results [n, naggs], rows_passed), rows sorted by
+        key ascending; only groups with a passing row appear."""
         import numpy as np
 
         np_ = len(preds)
@@ -946,7 +968,7 @@ class GpuContext:
             else:
                 pa[i] = self._PredSpec(col, op, lo, hi, 0, 0)
         na = len(aggs)
-        aa = (self._AggSpec * na)(*[self._AggSpec(c, o) for c, o in aggs])
+        aa = self._agg_specs(aggs)
         keys_out = np.zeros(max_groups, dtype=np.int64)
         out = (self._AggResult * (max_groups * na))()
         ng = C.c_uint64(0)

@@ -19,6 +19,9 @@
 // COUNT/SUM(i64) exact (wrap-around); SUM(f32) in f64 (atomic order
 // nondeterministic, like the reference's thread-order-dependent fp
 // aggregation; parity vs the oracle's sequential sum at ~1e-12 relative).
+// COUNT(col) / MIN / MAX (i64 and f32) are exact and order-independent:
+// MIN/MAX accumulate as one u64 atomicMax over order-preserving codes (see
+// agg_row), f32 in a NaN-greatest total order.
 
 #include <hip/hip_runtime.h>
 
@@ -150,7 +153,8 @@ struct ScanArgs {
   ColRef agg_col[SCAN_MAX_AGGS];
   int agg_op[SCAN_MAX_AGGS];
   int agg_src[SCAN_MAX_AGGS];  // 0=own col_read, 1+p=pred p's value, 9=key
-  const unsigned long long* agg_valid[SCAN_MAX_AGGS];  // SUM skips nulls
+  const unsigned long long* agg_valid[SCAN_MAX_AGGS];  // all but COUNT(*)
+                                                       // skip nulls
   unsigned long long* out;
   unsigned long long* rows_passed;
   // --- staged-FoR variant only (scan_agg_staged_kernel) ---
@@ -286,12 +290,100 @@ __device__ __forceinline__ void col_read2_lds(const SdbColGroupDescDev* desc,
   x1 = d.base + (int64_t)(bits_at(sw, bit0 + d.width) & mask);
 }
 
+// ---- MIN / MAX accumulator encoding -------------------------------------
+// Every MIN/MAX accumulator holds an unsigned "bigger wins" code whose
+// identity is 0, so all four ops are one u64 atomicMax (ds_max_u64 in LDS,
+// global_atomic_umax_x2 in HBM) on the same 8-byte slots the sums use, and
+// the zero fills of acc / d_out / gacc / neg_acc and the "skip a zero slot"
+// flushes stay valid. MAX_I64: x ^ 2^63 (signed order as unsigned);
+// MIN_I64: its complement. MAX_F32 / MIN_F32: the same pair over the
+// 32-bit total-order key of the NaN-canonicalised value. Code 0 decodes on
+// the host to the op's identity (agg_decode): for i64 it IS the identity's
+// code, and a canonicalised f32 can never produce it.
+#define SDB_I64_SIGN 0x8000000000000000ull
+
+// every NaN -> +qNaN 0x7FC00000, then IEEE total order as an unsigned key:
+// -inf < ... < -0.0 < +0.0 < ... < +inf < NaN. Keys span
+// [0x007FFFFF (-inf), 0xFFC00000 (NaN)]: neither 0 nor 0xFFFFFFFF occurs.
+__device__ __forceinline__ uint32_t f32_order_key(float f) {
+  uint32_t b = __float_as_uint(f);
+  if ((b & 0x7FFFFFFFu) > 0x7F800000u) b = 0x7FC00000u;
+  return b ^ ((b & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+// One row into one aggregate slot — the single statement of the per-row
+// aggregate switch, shared by every generic body (raw quad + tail, FoR pair
+// + odd tail, staged chunk + odd tail, hash LDS / global / key -1). geti /
+// getf fetch the row's i64 / f32 value the way the calling body does (own
+// read, decode-once reuse, LDS stage) and run only in the arm that needs
+// them. EXT = 0 is the [COUNT, SUM_I64, SUM_F64] switch exactly as it
+// stood before the ops >= SDB_AGG_COUNT_COL existed; the host launches
+// EXT = 1 instantiations only when the aggregate list holds such an op.
+template <int EXT, class GetI, class GetF>
+__device__ __forceinline__ void agg_row(unsigned long long* slot, int op,
+                                        const unsigned long long* valid,
+                                        uint64_t r, GetI geti, GetF getf) {
+  if (op != SDB_AGG_COUNT && !valid_at(valid, r))
+    return;  // every column aggregate skips NULLs; COUNT(*) counts the row
+  switch (op) {
+    case SDB_AGG_COUNT:
+      atomicAdd(slot, 1ull);
+      break;
+    case SDB_AGG_SUM_I64:
+      atomicAdd(slot, (unsigned long long)geti());
+      break;
+    case SDB_AGG_SUM_F64:
+      atomicAdd((double*)slot, (double)getf());
+      break;
+    default:
+      if (EXT) {
+        switch (op) {
+          case SDB_AGG_COUNT_COL:
+            atomicAdd(slot, 1ull);
+            break;
+          case SDB_AGG_MIN_I64:
+            atomicMax(slot, ~((unsigned long long)geti() ^ SDB_I64_SIGN));
+            break;
+          case SDB_AGG_MAX_I64:
+            atomicMax(slot, (unsigned long long)geti() ^ SDB_I64_SIGN);
+            break;
+          case SDB_AGG_MIN_F32:
+            atomicMax(slot, (unsigned long long)(~f32_order_key(getf())));
+            break;
+          case SDB_AGG_MAX_F32:
+            atomicMax(slot, (unsigned long long)f32_order_key(getf()));
+            break;
+        }
+      }
+      break;
+  }
+}
+
+// One partial (a workgroup's LDS slot) into its global slot: sums add,
+// MIN/MAX codes take the max. Zero partials (no row, or the identity) are
+// skipped.
+template <int EXT>
+__device__ __forceinline__ void agg_merge(unsigned long long* dst, int op,
+                                          unsigned long long v) {
+  if (op == SDB_AGG_SUM_F64) {
+    double d;
+    __builtin_memcpy(&d, &v, 8);
+    if (d != 0.0) atomicAdd((double*)dst, d);
+  } else if (v) {
+    if (EXT && op >= SDB_AGG_MIN_I64)
+      atomicMax(dst, v);
+    else
+      atomicAdd(dst, v);
+  }
+}
+
 // ASHAPE: compile-time aggregate-shape dispatch (DuckDB-style operator
 // specialization). 0 = generic runtime loop; 1 = the common 3-agg shape
 // [COUNT(*), SUM(i64), SUM(f32->f64)] with the per-row per-agg op/src
 // switches straight-lined (the FoR walker is instruction-issue-bound —
 // tools/ROUND2_NOTES.md). Any other shape falls back to ASHAPE=0.
-template <int RAW, int ASHAPE>
+// EXT: 1 = the aggregate list holds an op >= SDB_AGG_COUNT_COL (agg_row).
+template <int RAW, int ASHAPE, int EXT>
 __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* acc = (unsigned long long*)smem;  // ngroups*naggs
@@ -352,26 +444,11 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
                       (double)((const float*)a.agg_col[2].data)[r + e]);
           continue;
         }
-        for (uint32_t q = 0; q < a.naggs; ++q) {
-          unsigned long long* slot = &acc[g * a.naggs + q];
-          if (a.agg_op[q] != SDB_AGG_COUNT &&
-              !valid_at(a.agg_valid[q], r + e))
-            continue;  // SUM skips NULL values; COUNT(*) counts the row
-          switch (a.agg_op[q]) {
-            case SDB_AGG_COUNT:
-              atomicAdd(slot, 1ull);
-              break;
-            case SDB_AGG_SUM_I64:
-              atomicAdd(slot, (unsigned long long)((const long long*)
-                                                     a.agg_col[q]
-                                                       .data)[r + e]);
-              break;
-            case SDB_AGG_SUM_F64:
-              atomicAdd((double*)slot,
-                        (double)((const float*)a.agg_col[q].data)[r + e]);
-              break;
-          }
-        }
+        for (uint32_t q = 0; q < a.naggs; ++q)
+          agg_row<EXT>(
+            &acc[g * a.naggs + q], a.agg_op[q], a.agg_valid[q], r + e,
+            [&] { return ((const long long*)a.agg_col[q].data)[r + e]; },
+            [&] { return ((const float*)a.agg_col[q].data)[r + e]; });
       }
     }
     if ((a.rows & 3ull) && blockIdx.x == 0 && threadIdx.x == 0)
@@ -390,23 +467,11 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
       if (ok) {
         ++my_passed;
         const uint32_t g = (uint32_t)((const long long*)a.keys.data)[r];
-        for (uint32_t q = 0; q < a.naggs; ++q) {
-          unsigned long long* slot = &acc[g * a.naggs + q];
-          if (a.agg_op[q] != SDB_AGG_COUNT &&
-              !valid_at(a.agg_valid[q], r))
-            continue;
-          switch (a.agg_op[q]) {
-            case SDB_AGG_COUNT: atomicAdd(slot, 1ull); break;
-            case SDB_AGG_SUM_I64:
-              atomicAdd(slot, (unsigned long long)((const long long*)
-                                                     a.agg_col[q].data)[r]);
-              break;
-            case SDB_AGG_SUM_F64:
-              atomicAdd((double*)slot,
-                        (double)((const float*)a.agg_col[q].data)[r]);
-              break;
-          }
-        }
+        for (uint32_t q = 0; q < a.naggs; ++q)
+          agg_row<EXT>(
+            &acc[g * a.naggs + q], a.agg_op[q], a.agg_valid[q], r,
+            [&] { return ((const long long*)a.agg_col[q].data)[r]; },
+            [&] { return ((const float*)a.agg_col[q].data)[r]; });
       }
     }
     unsigned long long wp = my_passed;
@@ -414,16 +479,8 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
     for (int off = 32; off; off >>= 1) wp += __shfl_down(wp, off, 64);
     if ((threadIdx.x & 63) == 0 && wp) atomicAdd(a.rows_passed, wp);
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS) {
-      const uint32_t q = i % a.naggs;
-      if (a.agg_op[q] == SDB_AGG_SUM_F64) {
-        double v;
-        __builtin_memcpy(&v, &acc[i], 8);
-        if (v != 0.0) atomicAdd((double*)&a.out[i], v);
-      } else if (acc[i]) {
-        atomicAdd(&a.out[i], acc[i]);
-      }
-    }
+    for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS)
+      agg_merge<EXT>(&a.out[i], a.agg_op[i % a.naggs], acc[i]);
     return;
   }
 
@@ -524,32 +581,18 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
                       (double)((const float*)a.agg_col[2].data)[r + e]);
           continue;
         }
-        for (uint32_t q = 0; q < a.naggs; ++q) {
-          unsigned long long* slot = &acc[grp * a.naggs + q];
-          if (a.agg_op[q] != SDB_AGG_COUNT &&
-              !valid_at(a.agg_valid[q], r + e))
-            continue;
-          switch (a.agg_op[q]) {
-            case SDB_AGG_COUNT:
-              atomicAdd(slot, 1ull);
-              break;
-            case SDB_AGG_SUM_I64: {
-              int64_t x;
+        for (uint32_t q = 0; q < a.naggs; ++q)
+          agg_row<EXT>(
+            &acc[grp * a.naggs + q], a.agg_op[q], a.agg_valid[q], r + e,
+            [&]() -> int64_t {
               switch (a.agg_src[q]) {  // decode-once dedup vs preds/key
-                case 1: x = pva[e]; break;
-                case 2: x = pvb[e]; break;
-                case 9: x = ks[e]; break;
-                default: x = col_read(a.agg_col[q], rg, r0, r + e); break;
+                case 1: return pva[e];
+                case 2: return pvb[e];
+                case 9: return ks[e];
+                default: return col_read(a.agg_col[q], rg, r0, r + e);
               }
-              atomicAdd(slot, (unsigned long long)x);
-              break;
-            }
-            case SDB_AGG_SUM_F64:
-              atomicAdd((double*)slot,
-                        (double)((const float*)a.agg_col[q].data)[r + e]);
-              break;
-          }
-        }
+            },
+            [&] { return ((const float*)a.agg_col[q].data)[r + e]; });
       }
     }
     if ((glen & 1ull) && threadIdx.x == 0) {
@@ -589,30 +632,18 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
             atomicAdd((double*)(s3 + 2),
                       (double)((const float*)a.agg_col[2].data)[r]);
         } else
-        for (uint32_t q = 0; q < a.naggs; ++q) {
-          unsigned long long* slot = &acc[grp * a.naggs + q];
-          if (a.agg_op[q] != SDB_AGG_COUNT &&
-              !valid_at(a.agg_valid[q], r))
-            continue;
-          switch (a.agg_op[q]) {
-            case SDB_AGG_COUNT: atomicAdd(slot, 1ull); break;
-            case SDB_AGG_SUM_I64: {
-              int64_t x;
+        for (uint32_t q = 0; q < a.naggs; ++q)
+          agg_row<EXT>(
+            &acc[grp * a.naggs + q], a.agg_op[q], a.agg_valid[q], r,
+            [&]() -> int64_t {
               switch (a.agg_src[q]) {
-                case 1: x = pv0s; break;
-                case 2: x = pv1s; break;
-                case 9: x = (int64_t)grp; break;
-                default: x = col_read(a.agg_col[q], rg, r0, r); break;
+                case 1: return pv0s;
+                case 2: return pv1s;
+                case 9: return (int64_t)grp;
+                default: return col_read(a.agg_col[q], rg, r0, r);
               }
-              atomicAdd(slot, (unsigned long long)x);
-              break;
-            }
-            case SDB_AGG_SUM_F64:
-              atomicAdd((double*)slot,
-                        (double)((const float*)a.agg_col[q].data)[r]);
-              break;
-          }
-        }
+            },
+            [&] { return ((const float*)a.agg_col[q].data)[r]; });
       }
     }
   }
@@ -622,16 +653,8 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
   for (int off = 32; off; off >>= 1) wp += __shfl_down(wp, off, 64);
   if ((threadIdx.x & 63) == 0 && wp) atomicAdd(a.rows_passed, wp);
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS) {
-    const uint32_t q = i % a.naggs;
-    if (a.agg_op[q] == SDB_AGG_SUM_F64) {
-      double v;
-      __builtin_memcpy(&v, &acc[i], 8);
-      if (v != 0.0) atomicAdd((double*)&a.out[i], v);
-    } else if (acc[i]) {
-      atomicAdd(&a.out[i], acc[i]);
-    }
-  }
+  for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS)
+    agg_merge<EXT>(&a.out[i], a.agg_op[i % a.naggs], acc[i]);
 }
 
 // FoR walker with LDS payload staging: the plain walker (scan_agg_kernel<0>)
@@ -641,7 +664,7 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
 // are staged cooperatively (one coalesced burst per column), and all pair
 // extraction reads hit LDS. Zonemap skips, predicate fast path, and the
 // agg_src decode-once dedup are identical to the unstaged walker.
-template <int ASHAPE>
+template <int ASHAPE, int EXT>
 __launch_bounds__(SCAN_NTHREADS) __global__
 void scan_agg_staged_kernel(ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -787,37 +810,23 @@ void scan_agg_staged_kernel(ScanArgs a) {
             }
             continue;
           }
-          for (uint32_t q = 0; q < a.naggs; ++q) {
-            unsigned long long* slot = &acc[grp * a.naggs + q];
-            if (a.agg_op[q] != SDB_AGG_COUNT &&
-                !valid_at(a.agg_valid[q], r + e))
-              continue;
-            switch (a.agg_op[q]) {
-              case SDB_AGG_COUNT:
-                atomicAdd(slot, 1ull);
-                break;
-              case SDB_AGG_SUM_I64: {
-                int64_t x;
+          for (uint32_t q = 0; q < a.naggs; ++q)
+            agg_row<EXT>(
+              &acc[grp * a.naggs + q], a.agg_op[q], a.agg_valid[q], r + e,
+              [&]() -> int64_t {
                 switch (a.agg_src[q]) {  // decode-once dedup vs preds/key
-                  case 1: x = pva[e]; break;
-                  case 2: x = pvb[e]; break;
-                  case 9: x = ks[e]; break;
-                  default: x = col_read(a.agg_col[q], rg, r0, r + e); break;
+                  case 1: return pva[e];
+                  case 2: return pvb[e];
+                  case 9: return ks[e];
+                  default: return col_read(a.agg_col[q], rg, r0, r + e);
                 }
-                atomicAdd(slot, (unsigned long long)x);
-                break;
-              }
-              case SDB_AGG_SUM_F64: {
+              },
+              [&] {
                 const float* fc = (const float*)a.agg_col[q].data;
-                const float fv = fc == a.f32_pay
-                                   ? ((const float*)(sw +
-                                                     a.f32_lds_off))[lr + e]
-                                   : fc[r + e];
-                atomicAdd((double*)slot, (double)fv);
-                break;
-              }
-            }
-          }
+                return fc == a.f32_pay
+                         ? ((const float*)(sw + a.f32_lds_off))[lr + e]
+                         : fc[r + e];
+              });
         }
       }
     }
@@ -858,30 +867,18 @@ void scan_agg_staged_kernel(ScanArgs a) {
             atomicAdd((double*)(s3 + 2),
                       (double)((const float*)a.agg_col[2].data)[r]);
         } else
-        for (uint32_t q = 0; q < a.naggs; ++q) {
-          unsigned long long* slot = &acc[grp * a.naggs + q];
-          if (a.agg_op[q] != SDB_AGG_COUNT &&
-              !valid_at(a.agg_valid[q], r))
-            continue;
-          switch (a.agg_op[q]) {
-            case SDB_AGG_COUNT: atomicAdd(slot, 1ull); break;
-            case SDB_AGG_SUM_I64: {
-              int64_t x;
+        for (uint32_t q = 0; q < a.naggs; ++q)
+          agg_row<EXT>(
+            &acc[grp * a.naggs + q], a.agg_op[q], a.agg_valid[q], r,
+            [&]() -> int64_t {
               switch (a.agg_src[q]) {
-                case 1: x = pv0s; break;
-                case 2: x = pv1s; break;
-                case 9: x = (int64_t)grp; break;
-                default: x = col_read(a.agg_col[q], rg, r0, r); break;
+                case 1: return pv0s;
+                case 2: return pv1s;
+                case 9: return (int64_t)grp;
+                default: return col_read(a.agg_col[q], rg, r0, r);
               }
-              atomicAdd(slot, (unsigned long long)x);
-              break;
-            }
-            case SDB_AGG_SUM_F64:
-              atomicAdd((double*)slot,
-                        (double)((const float*)a.agg_col[q].data)[r]);
-              break;
-          }
-        }
+            },
+            [&] { return ((const float*)a.agg_col[q].data)[r]; });
       }
     }
   }
@@ -891,16 +888,8 @@ void scan_agg_staged_kernel(ScanArgs a) {
   for (int off = 32; off; off >>= 1) wp += __shfl_down(wp, off, 64);
   if ((threadIdx.x & 63) == 0 && wp) atomicAdd(a.rows_passed, wp);
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS) {
-    const uint32_t q = i % a.naggs;
-    if (a.agg_op[q] == SDB_AGG_SUM_F64) {
-      double v;
-      __builtin_memcpy(&v, &acc[i], 8);
-      if (v != 0.0) atomicAdd((double*)&a.out[i], v);
-    } else if (acc[i]) {
-      atomicAdd(&a.out[i], acc[i]);
-    }
-  }
+  for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS)
+    agg_merge<EXT>(&a.out[i], a.agg_op[i % a.naggs], acc[i]);
 }
 
 
@@ -979,29 +968,20 @@ __device__ __forceinline__ int64_t hash_global_upsert(
   return -1;
 }
 
+template <int EXT>
 __device__ __forceinline__ void hash_acc_add(const HashAggArgs& a,
                                              unsigned long long* acc,
                                              uint32_t q, uint32_t rg,
                                              uint64_t r0, uint64_t r,
                                              bool global_scope) {
-  if (a.agg_op[q] != SDB_AGG_COUNT && !valid_at(a.agg_valid[q], r))
-    return;  // SUM skips NULL values; COUNT(*) counts the row
-  switch (a.agg_op[q]) {
-    case SDB_AGG_COUNT:
-      atomicAdd(&acc[q], 1ull);
-      break;
-    case SDB_AGG_SUM_I64:
-      atomicAdd(&acc[q],
-                (unsigned long long)col_read(a.agg_col[q], rg, r0, r));
-      break;
-    case SDB_AGG_SUM_F64:
-      atomicAdd((double*)&acc[q],
-                (double)((const float*)a.agg_col[q].data)[r]);
-      break;
-  }
+  agg_row<EXT>(
+    &acc[q], a.agg_op[q], a.agg_valid[q], r,
+    [&] { return col_read(a.agg_col[q], rg, r0, r); },
+    [&] { return ((const float*)a.agg_col[q].data)[r]; });
   (void)global_scope;
 }
 
+template <int EXT>
 __launch_bounds__(SCAN_NTHREADS) __global__
 void scan_agg_hash_kernel(HashAggArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1059,7 +1039,7 @@ void scan_agg_hash_kernel(HashAggArgs a) {
                                __HIP_MEMORY_SCOPE_AGENT))
           atomicExch(&a.neg_acc[a.naggs], 1ull);
         for (uint32_t q = 0; q < a.naggs; ++q)
-          hash_acc_add(a, a.neg_acc, q, rg, r0, r, true);
+          hash_acc_add<EXT>(a, a.neg_acc, q, rg, r0, r, true);
         continue;
       }
       // LDS open-addressed probe (bounded), then global fallback
@@ -1084,17 +1064,17 @@ void scan_agg_hash_kernel(HashAggArgs a) {
         }
       }
       if (slot >= 0) {
-        hash_acc_add(a, &lacc[(uint32_t)slot * a.naggs], 0, rg, r0, r,
-                     false);
+        hash_acc_add<EXT>(a, &lacc[(uint32_t)slot * a.naggs], 0, rg, r0,
+                          r, false);
         for (uint32_t q = 1; q < a.naggs; ++q)
-          hash_acc_add(a, &lacc[(uint32_t)slot * a.naggs], q, rg, r0, r,
-                       false);
+          hash_acc_add<EXT>(a, &lacc[(uint32_t)slot * a.naggs], q, rg, r0,
+                            r, false);
       } else {
         const int64_t g = hash_global_upsert(a, k);
         if (g < 0) return;  // table overflow: host reports SDB_ERR_OOM
         for (uint32_t q = 0; q < a.naggs; ++q)
-          hash_acc_add(a, &a.gacc[(uint64_t)g * a.naggs], q, rg, r0, r,
-                       true);
+          hash_acc_add<EXT>(a, &a.gacc[(uint64_t)g * a.naggs], q, rg, r0,
+                            r, true);
       }
     }
   }
@@ -1110,17 +1090,9 @@ void scan_agg_hash_kernel(HashAggArgs a) {
     if (k == SDB_HKEY_EMPTY) continue;
     const int64_t g = hash_global_upsert(a, k);
     if (g < 0) return;
-    for (uint32_t q = 0; q < a.naggs; ++q) {
-      const unsigned long long v = lacc[i * a.naggs + q];
-      if (a.agg_op[q] == SDB_AGG_SUM_F64) {
-        double d;
-        __builtin_memcpy(&d, &v, 8);
-        if (d != 0.0)
-          atomicAdd((double*)&a.gacc[(uint64_t)g * a.naggs + q], d);
-      } else if (v) {
-        atomicAdd(&a.gacc[(uint64_t)g * a.naggs + q], v);
-      }
-    }
+    for (uint32_t q = 0; q < a.naggs; ++q)
+      agg_merge<EXT>(&a.gacc[(uint64_t)g * a.naggs + q], a.agg_op[q],
+                     lacc[i * a.naggs + q]);
   }
 }
 
@@ -1537,6 +1509,73 @@ int sdb_gpu_table_attach_strcol_fsst(SdbGpuCtx* ctx, SdbGpuTable* tab,
   return SDB_OK;
 }
 
+// Aggregate-list validation shared by every scan entry, run before anything
+// is launched: op inside SdbAggOp, column inside the table for every op but
+// COUNT(*), and the op's column type. *ext = the list holds an op >=
+// SDB_AGG_COUNT_COL, which selects the EXT = 1 kernel instantiations.
+static int agg_specs_check(const SdbGpuTable* tab, const SdbAggSpec* aggs,
+                           uint32_t naggs, bool* ext) {
+  if (!aggs) return SDB_ERR_INVALID;
+  *ext = false;
+  for (uint32_t q = 0; q < naggs; ++q) {
+    const uint32_t op = (uint32_t)aggs[q].op;
+    if (op > (uint32_t)SDB_AGG_MAX_F32) return SDB_ERR_INVALID;
+    if (op == SDB_AGG_COUNT) continue;
+    if (aggs[q].col >= tab->ncols) return SDB_ERR_INVALID;
+    const bool f32 = tab->types[aggs[q].col] == SDB_COL_F32;
+    switch (op) {
+      case SDB_AGG_SUM_I64:
+      case SDB_AGG_MIN_I64:
+      case SDB_AGG_MAX_I64:
+        if (f32) return SDB_ERR_INVALID;
+        break;
+      case SDB_AGG_SUM_F64:
+      case SDB_AGG_MIN_F32:
+      case SDB_AGG_MAX_F32:
+        if (!f32) return SDB_ERR_INVALID;
+        break;
+      default: break;  // COUNT_COL: any column type
+    }
+    *ext |= op >= (uint32_t)SDB_AGG_COUNT_COL;
+  }
+  return SDB_OK;
+}
+
+// device accumulator -> SdbAggResult. MIN/MAX slots hold "bigger wins"
+// codes (see agg_row); code 0 is the identity: INT64_MAX / INT64_MIN fall
+// out of the i64 decode, +inf / -inf are mapped here.
+static void agg_decode(int op, unsigned long long raw, SdbAggResult* r) {
+  r->i64 = 0;
+  r->f64 = 0;
+  switch (op) {
+    case SDB_AGG_SUM_F64:
+      std::memcpy(&r->f64, &raw, 8);
+      break;
+    case SDB_AGG_MIN_I64:
+      r->i64 = (int64_t)(~raw ^ SDB_I64_SIGN);
+      break;
+    case SDB_AGG_MAX_I64:
+      r->i64 = (int64_t)(raw ^ SDB_I64_SIGN);
+      break;
+    case SDB_AGG_MIN_F32:
+    case SDB_AGG_MAX_F32: {
+      const bool is_min = op == SDB_AGG_MIN_F32;
+      uint32_t bits = is_min ? 0x7F800000u : 0xFF800000u;  // +inf / -inf
+      if (raw) {
+        const uint32_t key = is_min ? ~(uint32_t)raw : (uint32_t)raw;
+        bits = (key & 0x80000000u) ? key ^ 0x80000000u : ~key;
+      }
+      float f;
+      std::memcpy(&f, &bits, 4);
+      r->f64 = (double)f;  // exact; keeps the sign of zero
+      break;
+    }
+    default:
+      r->i64 = (int64_t)raw;
+      break;
+  }
+}
+
 int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
                      uint32_t ngroups, const SdbPredSpec* preds,
                      uint32_t npreds, const SdbAggSpec* aggs, uint32_t naggs,
@@ -1545,6 +1584,8 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
       ngroups == 0 || ngroups > SCAN_MAX_GROUPS || naggs == 0 ||
       naggs > SCAN_MAX_AGGS || npreds > SCAN_MAX_PREDS)
     return SDB_ERR_INVALID;
+  bool ext = false;
+  if (agg_specs_check(tab, aggs, naggs, &ext)) return SDB_ERR_INVALID;
   if (tab->types[group_col] == SDB_COL_F32) return SDB_ERR_INVALID;
   if (tab->valid[group_col]) return SDB_ERR_INVALID;  // no NULL groups
   // dense-key contract: keys must be provably inside [0, ngroups) or the
@@ -1597,19 +1638,14 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
     a.agg_valid[q] =
       aggs[q].op == SDB_AGG_COUNT ? nullptr : tab->valid[aggs[q].col];
     a.agg_src[q] = 0;
-    if (aggs[q].op == SDB_AGG_SUM_I64) {
+    if (aggs[q].op == SDB_AGG_SUM_I64 || aggs[q].op == SDB_AGG_MIN_I64 ||
+        aggs[q].op == SDB_AGG_MAX_I64) {
       if (aggs[q].col == group_col) a.agg_src[q] = 9;
       for (uint32_t p = 0; p < npreds; ++p)
         if (preds[p].op != SDB_PRED_STRMASK &&  // str preds carry a SLOT
             aggs[q].col == preds[p].col)
           a.agg_src[q] = 1 + (int)p;
     }
-    if (aggs[q].op == SDB_AGG_SUM_I64 &&
-        tab->types[aggs[q].col] == SDB_COL_F32)
-      return SDB_ERR_INVALID;
-    if (aggs[q].op == SDB_AGG_SUM_F64 &&
-        tab->types[aggs[q].col] != SDB_COL_F32)
-      return SDB_ERR_INVALID;
   }
   const uint32_t nslots = ngroups * naggs;
   // ctx-cached workspace: the dense scan hot path allocates nothing per
@@ -1692,7 +1728,10 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
       if (!getenv("SDB_SCAN_NOF32STAGE") &&
           ldsb + 4ull * C + 16 <= 160 * 1024) {
         for (uint32_t q = 0; q < naggs; ++q) {
-          if (a.agg_op[q] == SDB_AGG_SUM_F64 && !a.agg_col[q].desc) {
+          if ((a.agg_op[q] == SDB_AGG_SUM_F64 ||
+               a.agg_op[q] == SDB_AGG_MIN_F32 ||
+               a.agg_op[q] == SDB_AGG_MAX_F32) &&
+              !a.agg_col[q].desc) {
             a.f32_pay = (const float*)a.agg_col[q].data;
             a.f32_lds_off = (uint32_t)(ldsb / 4);
             ldsb = (ldsb + 4ull * C + 15) & ~15ull;
@@ -1710,24 +1749,37 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
                       aggs[1].op == SDB_AGG_SUM_I64 &&
                       aggs[2].op == SDB_AGG_SUM_F64 &&
                       !getenv("SDB_SCAN_NOSHAPE");
+  // The last template argument (EXT) is set only when the list holds an op
+  // >= SDB_AGG_COUNT_COL: lists of the three original ops launch
+  // instantiations whose per-row switch has no arm for the new ones (a
+  // shape3 list never has one, so ASHAPE = 1 exists with EXT = 0 only).
   if (staged && shape3)
-    hipLaunchKernelGGL((scan_agg_staged_kernel<1>), dim3(nblocks),
+    hipLaunchKernelGGL((scan_agg_staged_kernel<1, 0>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
+  else if (staged && ext)
+    hipLaunchKernelGGL((scan_agg_staged_kernel<0, 1>), dim3(nblocks),
                        dim3(SCAN_NTHREADS), lds, stream, a);
   else if (staged)
-    hipLaunchKernelGGL((scan_agg_staged_kernel<0>), dim3(nblocks),
+    hipLaunchKernelGGL((scan_agg_staged_kernel<0, 0>), dim3(nblocks),
                        dim3(SCAN_NTHREADS), lds, stream, a);
   else if (any_for && shape3)
-    hipLaunchKernelGGL((scan_agg_kernel<0, 1>), dim3(nblocks),
+    hipLaunchKernelGGL((scan_agg_kernel<0, 1, 0>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
+  else if (any_for && ext)
+    hipLaunchKernelGGL((scan_agg_kernel<0, 0, 1>), dim3(nblocks),
                        dim3(SCAN_NTHREADS), lds, stream, a);
   else if (any_for)
-    hipLaunchKernelGGL((scan_agg_kernel<0, 0>), dim3(nblocks),
+    hipLaunchKernelGGL((scan_agg_kernel<0, 0, 0>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
+  else if (ext)
+    hipLaunchKernelGGL((scan_agg_kernel<1, 0, 1>), dim3(nblocks),
                        dim3(SCAN_NTHREADS), lds, stream, a);
   else
     // RAW stays generic: the straight-lined 3-agg arm measured 183G vs
     // 234G rows/s on the same box (r2_raw_shape_ab.log) — the runtime
     // agg loop bounds the e-unroll better there; only the
     // instruction-bound FoR walkers keep ASHAPE=1
-    hipLaunchKernelGGL((scan_agg_kernel<1, 0>), dim3(nblocks),
+    hipLaunchKernelGGL((scan_agg_kernel<1, 0, 0>), dim3(nblocks),
                        dim3(SCAN_NTHREADS), lds, stream, a);
   HIP_CHECK_CLEAN(hipGetLastError());
   std::vector<unsigned long long> h_out(nslots);
@@ -1740,19 +1792,8 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
 #undef HIP_CHECK_CLEAN
   // d_out/d_passed are ctx-cached; freed with the context
   for (uint32_t g = 0; g < ngroups; ++g) {
-    for (uint32_t q = 0; q < naggs; ++q) {
-      const unsigned long long raw = h_out[g * naggs + q];
-      SdbAggResult* r = &out[g * naggs + q];
-      if (aggs[q].op == SDB_AGG_SUM_F64) {
-        double v;
-        std::memcpy(&v, &raw, 8);
-        r->f64 = v;
-        r->i64 = 0;
-      } else {
-        r->i64 = (int64_t)raw;
-        r->f64 = 0;
-      }
-    }
+    for (uint32_t q = 0; q < naggs; ++q)
+      agg_decode(aggs[q].op, h_out[g * naggs + q], &out[g * naggs + q]);
   }
   *rows_passed = h_passed;
   return SDB_OK;
@@ -1772,6 +1813,8 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
       max_groups == 0 || max_groups > (1u << 22) || naggs == 0 ||
       naggs > SCAN_MAX_AGGS || npreds > SCAN_MAX_PREDS)
     return SDB_ERR_INVALID;
+  bool ext = false;
+  if (agg_specs_check(tab, aggs, naggs, &ext)) return SDB_ERR_INVALID;
 
   hipStream_t stream = ctx->stream;
   HashAggArgs a{};
@@ -1812,12 +1855,6 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
                                                : tab->refs[aggs[q].col];
     a.agg_valid[q] =
       aggs[q].op == SDB_AGG_COUNT ? nullptr : tab->valid[aggs[q].col];
-    if (aggs[q].op == SDB_AGG_SUM_I64 &&
-        tab->types[aggs[q].col] == SDB_COL_F32)
-      return SDB_ERR_INVALID;
-    if (aggs[q].op == SDB_AGG_SUM_F64 &&
-        tab->types[aggs[q].col] != SDB_COL_F32)
-      return SDB_ERR_INVALID;
   }
   // global table: pow2 capacity >= 2*max_groups (load factor <= 0.5)
   uint64_t cap = 64;
@@ -1870,8 +1907,12 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
     (uint32_t)((tab->rows + a.group_rows - 1) / a.group_rows);
   if (nblocks > SCAN_MAXB) nblocks = SCAN_MAXB;
   if (nblocks < 1) nblocks = 1;
-  hipLaunchKernelGGL(scan_agg_hash_kernel, dim3(nblocks),
-                     dim3(SCAN_NTHREADS), lds, stream, a);
+  if (ext)  // as in sdb_gpu_scan_agg: old-op lists keep the old switch
+    hipLaunchKernelGGL((scan_agg_hash_kernel<1>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
+  else
+    hipLaunchKernelGGL((scan_agg_hash_kernel<0>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
   HASH_CHECK(hipGetLastError());
 
   std::vector<unsigned long long> h_keys(cap);
@@ -1906,18 +1947,8 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
   uint64_t n = 0;
   auto emit = [&](int64_t key, const unsigned long long* acc) {
     keys_out[n] = key;
-    for (uint32_t q = 0; q < naggs; ++q) {
-      SdbAggResult* r = &out[n * naggs + q];
-      if (aggs[q].op == SDB_AGG_SUM_F64) {
-        double v;
-        std::memcpy(&v, &acc[q], 8);
-        r->f64 = v;
-        r->i64 = 0;
-      } else {
-        r->i64 = (int64_t)acc[q];
-        r->f64 = 0;
-      }
-    }
+    for (uint32_t q = 0; q < naggs; ++q)
+      agg_decode(aggs[q].op, acc[q], &out[n * naggs + q]);
     ++n;
   };
   // negative keys sort before -1? No: -1 is the LARGEST negative value,
@@ -2023,6 +2054,11 @@ int sdb_gpu_scan_agg_hash_str(SdbGpuCtx* ctx, SdbGpuTable* tab,
                               uint64_t* rows_passed) {
   if (!ctx || !tab || str_slot >= SDB_MAX_STRCOLS ||
       !tab->str_off[str_slot])
+    return SDB_ERR_INVALID;
+  // the core repeats this; here it keeps a bad list from launching the
+  // hash kernel first
+  bool ext = false;
+  if (naggs > SCAN_MAX_AGGS || agg_specs_check(tab, aggs, naggs, &ext))
     return SDB_ERR_INVALID;
   long long* d_hash = nullptr;
   HIP_CHECK(hipMalloc(&d_hash, 8ull * (tab->rows ? tab->rows : 1)));
