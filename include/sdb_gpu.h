@@ -303,8 +303,11 @@ int sdb_gpu_table_free(SdbGpuCtx* ctx, SdbGpuTable* tab);
  * NULL rows; SDB_PRED_ISNULL / SDB_PRED_NOTNULL evaluate the validity
  * plane alone; SUM aggregates skip NULL values while COUNT(*) counts the
  * row. bit r of bits[r>>6] set = row r VALID; (rows+63)/64 words. NULL
- * detaches (all valid). Validity on the GROUP-KEY column is rejected at
- * scan time (NULL-group semantics not implemented). */
+ * detaches (all valid). A plane on the GROUP-KEY column makes the key
+ * nullable: sdb_gpu_scan_agg_nullkey and sdb_gpu_scan_agg_hash_nullkey
+ * put every passing NULL-key row into one NULL group, whatever value the
+ * row stores; sdb_gpu_scan_agg and sdb_gpu_scan_agg_hash have no place
+ * for that group and return SDB_ERR_INVALID for such a column. */
 int sdb_gpu_table_attach_validity(SdbGpuCtx* ctx, SdbGpuTable* tab,
                                   uint32_t col, const uint64_t* bits);
 
@@ -436,6 +439,53 @@ int sdb_gpu_scan_agg_hash(SdbGpuCtx* ctx, SdbGpuTable* tab,
                           int64_t* keys_out /* max_groups */,
                           SdbAggResult* out /* max_groups*naggs */,
                           uint64_t* ngroups_out, uint64_t* rows_passed);
+
+/* ---- GROUP BY a nullable key ----
+ * The two entries above with a NULL group, as the DuckDB hash-aggregate
+ * consumer forms it: a passing row whose key validity bit is cleared
+ * belongs to the NULL group. Its stored key is never an index, a hash key
+ * or an aggregate input, so it may equal a live key or -1 or lie outside
+ * [0, ngroups). Predicates on the key column keep their meaning (a compare
+ * drops NULL-key rows, ISNULL keeps only them, NOTNULL empties the NULL
+ * group), and so do aggregates over it: in the NULL group COUNT_COL(key)
+ * and SUM_I64(key) are 0 and MIN / MAX return their identities.
+ * *rows_passed counts NULL-key rows like any other passing row;
+ * *null_rows is how many of them there were. A key column with no plane
+ * attached is accepted too: *null_rows == 0 and the key groups are those
+ * of the entry above.
+ *
+ * Dense: valid keys must lie in [0, ngroups), proved before launch from
+ * the column's range over its VALID rows (one reduction per attached
+ * plane, at the first such scan; a column with no valid row proves
+ * trivially); a valid key outside returns SDB_ERR_INVALID.
+ *
+ * Hash: the NULL group is separate from every key group, key -1
+ * included, and does not count against max_groups.
+ *
+ * Across shards the NULL group merges like any other group: sums add,
+ * MIN_* take the min, MAX_* the max. */
+
+/* out holds (ngroups + 1) * naggs results: row ngroups is the NULL group.
+ * *null_rows = passing rows whose key is NULL (0 = no NULL group). */
+int sdb_gpu_scan_agg_nullkey(SdbGpuCtx* ctx, SdbGpuTable* tab,
+                             uint32_t group_col, uint32_t ngroups,
+                             const SdbPredSpec* preds, uint32_t npreds,
+                             const SdbAggSpec* aggs, uint32_t naggs,
+                             SdbAggResult* out /* (ngroups+1)*naggs */,
+                             uint64_t* rows_passed, uint64_t* null_rows);
+
+/* keys_out/out as in sdb_gpu_scan_agg_hash (key groups only, ascending);
+ * null_out[naggs] = the NULL group, identities/zeros if *null_rows == 0. */
+int sdb_gpu_scan_agg_hash_nullkey(SdbGpuCtx* ctx, SdbGpuTable* tab,
+                                  uint32_t group_col, uint64_t max_groups,
+                                  const SdbPredSpec* preds, uint32_t npreds,
+                                  const SdbAggSpec* aggs, uint32_t naggs,
+                                  int64_t* keys_out /* max_groups */,
+                                  SdbAggResult* out /* max_groups*naggs */,
+                                  uint64_t* ngroups_out,
+                                  uint64_t* rows_passed,
+                                  SdbAggResult* null_out /* naggs */,
+                                  uint64_t* null_rows);
 
 /* GROUP BY string keys over an attached raw or FSST string slot (the
  * reference hands text group-by to its DuckDB fork's hash aggregate —

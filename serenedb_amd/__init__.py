@@ -984,6 +984,73 @@ class GpuContext:
         i64, f64 = self._unpack_aggs(out, n, na)
         return keys_out[:n], i64, f64, passed.value
 
+    # ---- GROUP BY a nullable key (a validity plane on the group column) ----
+
+    def _pred_specs(self, preds):
+        """[(col, op, lo, hi)] -> SdbPredSpec array (at least one slot)"""
+        pa = (self._PredSpec * max(len(preds), 1))()
+        for i, (col, op, lo, hi) in enumerate(preds):
+            if isinstance(lo, float) or isinstance(hi, float):
+                pa[i] = self._PredSpec(col, op, 0, 0, lo, hi)
+            else:
+                pa[i] = self._PredSpec(col, op, lo, hi, 0, 0)
+        return pa
+
+    def scan_agg_nullkey(self, tab, group_col, ngroups, preds, aggs):
+        """scan_agg for a group column that may carry a validity plane:
+        every passing row whose key is NULL lands in one NULL group,
+        whatever value the row stores. preds / aggs as in scan_agg.
+        Returns (i64 [ngroups+1, naggs], f64 [ngroups+1, naggs],
+        rows_passed, null_rows): row ngroups is the NULL group (zeros and
+        identities when null_rows == 0), rows_passed includes the NULL-key
+        rows. Valid keys must lie in [0, ngroups). Without a plane the
+        first ngroups rows are scan_agg's."""
+        na = len(aggs)
+        out = (self._AggResult * ((ngroups + 1) * na))()
+        passed = C.c_uint64(0)
+        nulls = C.c_uint64(0)
+        rc = self._lib.sdb_gpu_scan_agg_nullkey(
+            self._ctx, tab, C.c_uint32(group_col), C.c_uint32(ngroups),
+            self._pred_specs(preds), C.c_uint32(len(preds)),
+            self._agg_specs(aggs), C.c_uint32(na), out, C.byref(passed),
+            C.byref(nulls))
+        if rc != 0:
+            raise RuntimeError(f"sdb_gpu_scan_agg_nullkey rc={rc}")
+        i64, f64 = self._unpack_aggs(out, ngroups + 1, na)
+        return i64, f64, passed.value, nulls.value
+
+    def scan_agg_hash_nullkey(self, tab, group_col, max_groups, preds,
+                              aggs):
+        """scan_agg_hash for a group column that may carry a validity
+        plane. Returns (keys[n], i64 [n, naggs], f64 [n, naggs],
+        rows_passed, null_i64 [naggs], null_f64 [naggs], null_rows): the
+        key groups as scan_agg_hash returns them (valid keys only,
+        ascending), then the NULL group, which exists iff null_rows > 0
+        (zeros and identities otherwise). The NULL group is no key group:
+        it is apart from key -1 and takes no share of max_groups."""
+        import numpy as np
+
+        na = len(aggs)
+        keys_out = np.zeros(max_groups, dtype=np.int64)
+        out = (self._AggResult * (max_groups * na))()
+        null_out = (self._AggResult * na)()
+        ng = C.c_uint64(0)
+        passed = C.c_uint64(0)
+        nulls = C.c_uint64(0)
+        rc = self._lib.sdb_gpu_scan_agg_hash_nullkey(
+            self._ctx, tab, C.c_uint32(group_col), C.c_uint64(max_groups),
+            self._pred_specs(preds), C.c_uint32(len(preds)),
+            self._agg_specs(aggs), C.c_uint32(na),
+            keys_out.ctypes.data_as(C.POINTER(C.c_int64)), out,
+            C.byref(ng), C.byref(passed), null_out, C.byref(nulls))
+        if rc != 0:
+            raise RuntimeError(f"sdb_gpu_scan_agg_hash_nullkey rc={rc}")
+        n = ng.value
+        i64, f64 = self._unpack_aggs(out, n, na)
+        ni64, nf64 = self._unpack_aggs(null_out, 1, na)
+        return (keys_out[:n], i64, f64, passed.value, ni64[0], nf64[0],
+                nulls.value)
+
 
     def execute_topk_batch(self, segs, term_idx, boosts, k, nq,
                            min_match=1, k1=1.2, b=0.75, global_stats=None,

@@ -20,7 +20,7 @@ struct SdbGpuCtx {
   // allocation-free across calls (grown on demand, freed with the ctx)
   unsigned long long* d_scan_out;
   uint64_t scan_out_cap;  // slots
-  unsigned long long* d_scan_passed;
+  unsigned long long* d_scan_passed;  // [2]: rows passed, NULL-key rows
   SdbScoreDoc* d_cands;
   uint32_t* d_cand_count;
   unsigned long long* d_total_matches;

@@ -92,6 +92,12 @@ struct SdbGpuTable {
   int64_t col_min[16], col_max[16];
   uint8_t has_minmax[16];
   unsigned long long* valid[16];  // device validity bitmaps or null
+  // i64 column value range over the VALID rows of the attached plane: the
+  // same proof for a nullable group key, whose NULL rows may hold anything.
+  // One GPU reduction at the first nullable-key scan after an attach;
+  // dropped by every attach / detach. vmin > vmax = no valid row.
+  int64_t valid_min[16], valid_max[16];
+  uint8_t has_valid_minmax[16];
   uint32_t ncols;
   uint64_t rows;
   uint32_t group_rows;   // shared by every FoR column (0 if none)
@@ -173,6 +179,16 @@ struct ScanArgs {
   const float* f32_pay;     // null = no f32 staging
   uint32_t f32_lds_off;
 };
+
+// Kernel argument of the nullable-group-key (NK = 1) instantiations. The
+// NK = 0 ones keep taking ScanArgs itself, so their kernel-argument segment
+// — and with it every offset they load from — is what it was.
+struct ScanArgsNK : ScanArgs {
+  const unsigned long long* key_valid;  // the key column's own plane
+  unsigned long long* null_rows;        // passing rows whose key is NULL
+};
+template <int NK> struct ScanArgsOf { using type = ScanArgs; };
+template <> struct ScanArgsOf<1> { using type = ScanArgsNK; };
 
 // predicate evaluation — the SdbPredOp set mirrors the reference's pushed
 // table filters (index/table_filter_iterator.hpp:104-227: typed compares;
@@ -290,6 +306,37 @@ __device__ __forceinline__ void col_read2_lds(const SdbColGroupDescDev* desc,
   x1 = d.base + (int64_t)(bits_at(sw, bit0 + d.width) & mask);
 }
 
+// min/max of a raw or FoR i64 column over its VALID rows only: the range
+// proof of a nullable group key (NULL rows may hold anything). Run once per
+// attached plane, never per scan. mm as in col_minmax_kernel; a column with
+// no valid row leaves the {~0, 0} fill, i.e. min > max.
+__global__ void col_minmax_valid_kernel(ColRef c,
+                                        const unsigned long long* valid,
+                                        uint64_t n, uint32_t group_rows,
+                                        unsigned long long* __restrict__ mm) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  long long lmin = 0x7FFFFFFFFFFFFFFFll, lmax = 0x8000000000000000ll;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    if (!valid_at(valid, i)) continue;
+    const uint32_t rg = (uint32_t)(i / group_rows);
+    const long long x = col_read(c, rg, (uint64_t)rg * group_rows, i);
+    lmin = x < lmin ? x : lmin;
+    lmax = x > lmax ? x : lmax;
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const long long a = __shfl_down(lmin, off, 64);
+    const long long b = __shfl_down(lmax, off, 64);
+    lmin = a < lmin ? a : lmin;
+    lmax = b > lmax ? b : lmax;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMin(&mm[0], (unsigned long long)lmin ^ 0x8000000000000000ull);
+    atomicMax(&mm[1], (unsigned long long)lmax ^ 0x8000000000000000ull);
+  }
+}
+
 // ---- MIN / MAX accumulator encoding -------------------------------------
 // Every MIN/MAX accumulator holds an unsigned "bigger wins" code whose
 // identity is 0, so all four ops are one u64 atomicMax (ds_max_u64 in LDS,
@@ -383,11 +430,36 @@ __device__ __forceinline__ void agg_merge(unsigned long long* dst, int op,
 // switches straight-lined (the FoR walker is instruction-issue-bound —
 // tools/ROUND2_NOTES.md). Any other shape falls back to ASHAPE=0.
 // EXT: 1 = the aggregate list holds an op >= SDB_AGG_COUNT_COL (agg_row).
-template <int RAW, int ASHAPE, int EXT>
-__launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
+// NK: 1 = the key column carries a validity plane (a.key_valid): a row whose
+// key bit is cleared goes to the NULL group, accumulator row ngroups. NK = 1
+// exists with ASHAPE = 0, EXT = 1 only; NK = 0 is the code as it stood.
+
+// The accumulator row of a passing row, chosen before anything is indexed:
+// the stored key of a NULL-key row may be any value and is never used.
+template <int NK>
+__device__ __forceinline__ uint32_t key_group(
+  const typename ScanArgsOf<NK>::type& a, uint32_t key, uint64_t r) {
+  if constexpr (NK) {
+    if (!valid_at(a.key_valid, r)) return a.ngroups;
+  }
+  return key;
+}
+
+// NULL-key passing rows of a workgroup into a.null_rows (NK = 1 only)
+__device__ __forceinline__ void null_rows_flush(unsigned long long* dst,
+                                                unsigned long long mine) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) mine += __shfl_down(mine, off, 64);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(dst, mine);
+}
+
+template <int RAW, int ASHAPE, int EXT, int NK = 0>
+__launch_bounds__(SCAN_NTHREADS) __global__
+void scan_agg_kernel(typename ScanArgsOf<NK>::type a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* acc = (unsigned long long*)smem;  // ngroups*naggs
-  const uint32_t nslots = a.ngroups * a.naggs;
+  const uint32_t nslots = (a.ngroups + (NK ? 1u : 0u)) * a.naggs;
+  unsigned long long my_null = 0;  // NK: passing rows with a NULL key
   for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS) acc[i] = 0;
   __syncthreads();
 
@@ -431,7 +503,11 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
       for (int e = 0; e < 4; ++e) {
         if (!okv[e]) continue;
         ++my_passed;
-        const uint32_t g = (uint32_t)ks[e];
+        uint32_t g = (uint32_t)ks[e];
+        if constexpr (NK) {
+          g = key_group<NK>(a, g, r + e);
+          my_null += g == a.ngroups;  // valid keys are proved < ngroups
+        }
         if (ASHAPE == 1) {  // straight-lined 3-agg shape (dead if generic)
           unsigned long long* s3 = &acc[g * 3u];
           atomicAdd(s3, 1ull);
@@ -466,7 +542,11 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
       }
       if (ok) {
         ++my_passed;
-        const uint32_t g = (uint32_t)((const long long*)a.keys.data)[r];
+        uint32_t g = (uint32_t)((const long long*)a.keys.data)[r];
+        if constexpr (NK) {
+          g = key_group<NK>(a, g, r);
+          my_null += g == a.ngroups;
+        }
         for (uint32_t q = 0; q < a.naggs; ++q)
           agg_row<EXT>(
             &acc[g * a.naggs + q], a.agg_op[q], a.agg_valid[q], r,
@@ -478,6 +558,7 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
 #pragma unroll
     for (int off = 32; off; off >>= 1) wp += __shfl_down(wp, off, 64);
     if ((threadIdx.x & 63) == 0 && wp) atomicAdd(a.rows_passed, wp);
+    if constexpr (NK) null_rows_flush(a.null_rows, my_null);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS)
       agg_merge<EXT>(&a.out[i], a.agg_op[i % a.naggs], acc[i]);
@@ -562,7 +643,11 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
       for (int e = 0; e < 2; ++e) {
         if (!okv[e]) continue;
         ++my_passed;
-        const uint32_t grp = (uint32_t)ks[e];
+        uint32_t grp = (uint32_t)ks[e];
+        if constexpr (NK) {
+          grp = key_group<NK>(a, grp, r + e);
+          my_null += grp == a.ngroups;
+        }
         if (ASHAPE == 1) {  // straight-lined 3-agg shape (dead if generic)
           unsigned long long* s3 = &acc[grp * 3u];
           atomicAdd(s3, 1ull);
@@ -614,7 +699,13 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
       }
       if (ok) {
         ++my_passed;
-        const uint32_t grp = (uint32_t)col_read(a.keys, rg, r0, r);
+        // NK: a NULL key gives grp == ngroups; agg_src 9 then never reads
+        // grp as a value, agg_row having skipped the NULL first
+        uint32_t grp = (uint32_t)col_read(a.keys, rg, r0, r);
+        if constexpr (NK) {
+          grp = key_group<NK>(a, grp, r);
+          my_null += grp == a.ngroups;
+        }
         if (ASHAPE == 1) {  // straight-lined 3-agg shape
           unsigned long long* s3 = &acc[grp * 3u];
           atomicAdd(s3, 1ull);
@@ -652,6 +743,7 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
 #pragma unroll
   for (int off = 32; off; off >>= 1) wp += __shfl_down(wp, off, 64);
   if ((threadIdx.x & 63) == 0 && wp) atomicAdd(a.rows_passed, wp);
+  if constexpr (NK) null_rows_flush(a.null_rows, my_null);
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS)
     agg_merge<EXT>(&a.out[i], a.agg_op[i % a.naggs], acc[i]);
@@ -664,13 +756,14 @@ __launch_bounds__(SCAN_NTHREADS) __global__ void scan_agg_kernel(ScanArgs a) {
 // are staged cooperatively (one coalesced burst per column), and all pair
 // extraction reads hit LDS. Zonemap skips, predicate fast path, and the
 // agg_src decode-once dedup are identical to the unstaged walker.
-template <int ASHAPE, int EXT>
+template <int ASHAPE, int EXT, int NK = 0>
 __launch_bounds__(SCAN_NTHREADS) __global__
-void scan_agg_staged_kernel(ScanArgs a) {
+void scan_agg_staged_kernel(typename ScanArgsOf<NK>::type a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* acc = (unsigned long long*)smem;  // ngroups*naggs
   uint32_t* sw = (uint32_t*)smem;  // stage buffers live past acc
-  const uint32_t nslots = a.ngroups * a.naggs;
+  const uint32_t nslots = (a.ngroups + (NK ? 1u : 0u)) * a.naggs;
+  unsigned long long my_null = 0;  // NK: passing rows with a NULL key
   for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS) acc[i] = 0;
   __syncthreads();  // a 1-row group accumulates before any chunk barrier
 
@@ -786,7 +879,11 @@ void scan_agg_staged_kernel(ScanArgs a) {
         for (int e = 0; e < 2; ++e) {
           if (!okv[e]) continue;
           ++my_passed;
-          const uint32_t grp = (uint32_t)ks[e];
+          uint32_t grp = (uint32_t)ks[e];
+          if constexpr (NK) {
+            grp = key_group<NK>(a, grp, r + e);
+            my_null += grp == a.ngroups;
+          }
           if (ASHAPE == 1) {  // straight-lined 3-agg shape
             unsigned long long* s3 = &acc[grp * 3u];
             atomicAdd(s3, 1ull);
@@ -849,7 +946,13 @@ void scan_agg_staged_kernel(ScanArgs a) {
       }
       if (ok) {
         ++my_passed;
-        const uint32_t grp = (uint32_t)col_read(a.keys, rg, r0, r);
+        // NK: a NULL key gives grp == ngroups; agg_src 9 then never reads
+        // grp as a value, agg_row having skipped the NULL first
+        uint32_t grp = (uint32_t)col_read(a.keys, rg, r0, r);
+        if constexpr (NK) {
+          grp = key_group<NK>(a, grp, r);
+          my_null += grp == a.ngroups;
+        }
         if (ASHAPE == 1) {  // straight-lined 3-agg shape
           unsigned long long* s3 = &acc[grp * 3u];
           atomicAdd(s3, 1ull);
@@ -887,6 +990,7 @@ void scan_agg_staged_kernel(ScanArgs a) {
 #pragma unroll
   for (int off = 32; off; off >>= 1) wp += __shfl_down(wp, off, 64);
   if ((threadIdx.x & 63) == 0 && wp) atomicAdd(a.rows_passed, wp);
+  if constexpr (NK) null_rows_flush(a.null_rows, my_null);
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < nslots; i += SCAN_NTHREADS)
     agg_merge<EXT>(&a.out[i], a.agg_op[i % a.naggs], acc[i]);
@@ -945,6 +1049,16 @@ struct HashAggArgs {
   uint32_t lds_slots;   // pow2 (0 = LDS staging disabled)
 };
 
+// argument of the nullable-group-key (NK = 1) instantiation; NK = 0 keeps
+// HashAggArgs itself (see ScanArgsNK)
+struct HashAggArgsNK : HashAggArgs {
+  const unsigned long long* key_valid;  // the key column's own plane
+  unsigned long long* null_acc;  // [naggs+1]: NULL-group accumulators +
+                                 // count of passing NULL-key rows
+};
+template <int NK> struct HashAggArgsOf { using type = HashAggArgs; };
+template <> struct HashAggArgsOf<1> { using type = HashAggArgsNK; };
+
 // probe/insert into the global table; returns slot or -1 (overflow).
 __device__ __forceinline__ int64_t hash_global_upsert(
   const HashAggArgs& a, uint64_t k) {
@@ -981,16 +1095,27 @@ __device__ __forceinline__ void hash_acc_add(const HashAggArgs& a,
   (void)global_scope;
 }
 
-template <int EXT>
+// NK: 1 = the key column carries a validity plane (a.key_valid). A passing
+// row whose key bit is cleared feeds the NULL group and nothing else: its
+// stored key is not read, so it can light neither the key -1 group nor a
+// table slot. The NULL group follows the key -1 pattern — [naggs]
+// accumulators plus a word in the misc buffer (a.null_acc), here the count
+// of such rows — with one difference: a quarter of all rows may be NULL,
+// so each workgroup accumulates them in LDS (lnull, past the table) and
+// merges once at the end, where key -1 rows go to global one by one.
+template <int EXT, int NK = 0>
 __launch_bounds__(SCAN_NTHREADS) __global__
-void scan_agg_hash_kernel(HashAggArgs a) {
+void scan_agg_hash_kernel(typename HashAggArgsOf<NK>::type a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* lkey = (unsigned long long*)smem;     // lds_slots
   unsigned long long* lacc = lkey + a.lds_slots;            // slots*naggs
+  unsigned long long* lnull = lacc + a.lds_slots * a.naggs;  // NK: naggs
   const uint32_t S_mask = a.lds_slots ? a.lds_slots - 1 : 0;
   for (uint32_t i = threadIdx.x; i < a.lds_slots * (1 + a.naggs);
        i += SCAN_NTHREADS)
     lkey[i] = i < a.lds_slots ? SDB_HKEY_EMPTY : 0ull;
+  if (NK && threadIdx.x < a.naggs) lnull[threadIdx.x] = 0ull;
+  unsigned long long my_null = 0;  // NK: passing rows with a NULL key
   __syncthreads();
 
   const uint32_t n_rowgroups =
@@ -1033,6 +1158,14 @@ void scan_agg_hash_kernel(HashAggArgs a) {
       }
       if (!ok) continue;
       ++my_passed;
+      if constexpr (NK) {
+        if (!valid_at(a.key_valid, r)) {  // NULL key: before key -1
+          ++my_null;
+          for (uint32_t q = 0; q < a.naggs; ++q)
+            hash_acc_add<EXT>(a, lnull, q, rg, r0, r, false);
+          continue;
+        }
+      }
       const uint64_t k = (uint64_t)col_read(a.keys, rg, r0, r);
       if (k == SDB_HKEY_EMPTY) {  // actual key -1: dedicated accumulators
         if (!__hip_atomic_load(&a.neg_acc[a.naggs], __ATOMIC_RELAXED,
@@ -1083,7 +1216,13 @@ void scan_agg_hash_kernel(HashAggArgs a) {
 #pragma unroll
   for (int off = 32; off; off >>= 1) wp += __shfl_down(wp, off, 64);
   if ((threadIdx.x & 63) == 0 && wp) atomicAdd(a.rows_passed, wp);
+  if constexpr (NK) null_rows_flush(&a.null_acc[a.naggs], my_null);
   __syncthreads();
+  if constexpr (NK) {  // the workgroup's NULL group into the global one
+    if (threadIdx.x < a.naggs)
+      agg_merge<EXT>(&a.null_acc[threadIdx.x], a.agg_op[threadIdx.x],
+                     lnull[threadIdx.x]);
+  }
   // flush the LDS table into the global table
   for (uint32_t i = threadIdx.x; i < a.lds_slots; i += SCAN_NTHREADS) {
     const unsigned long long k = lkey[i];
@@ -1235,6 +1374,7 @@ int sdb_gpu_table_free(SdbGpuCtx* ctx, SdbGpuTable* tab) {
 int sdb_gpu_table_attach_validity(SdbGpuCtx* ctx, SdbGpuTable* tab,
                                   uint32_t col, const uint64_t* bits) {
   if (!ctx || !tab || col >= tab->ncols) return SDB_ERR_INVALID;
+  tab->has_valid_minmax[col] = 0;  // the valid-rows range dies with the plane
   if (!bits) {
     if (tab->valid[col]) (void)hipFree(tab->valid[col]);
     tab->valid[col] = nullptr;
@@ -1576,10 +1716,45 @@ static void agg_decode(int op, unsigned long long raw, SdbAggResult* r) {
   }
 }
 
-int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
-                     uint32_t ngroups, const SdbPredSpec* preds,
-                     uint32_t npreds, const SdbAggSpec* aggs, uint32_t naggs,
-                     SdbAggResult* out, uint64_t* rows_passed) {
+// The range of column col over the valid rows of its attached plane, cached
+// on the table: one reduction per attached plane (attach_validity drops it),
+// so a nullable-key scan in steady state runs no extra pass and allocates
+// nothing.
+static int valid_minmax(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t col) {
+  if (tab->has_valid_minmax[col]) return SDB_OK;
+  unsigned long long* d_mm = nullptr;
+  HIP_CHECK(hipMalloc(&d_mm, 16));
+  const unsigned long long init[2] = {~0ull, 0ull};
+  unsigned long long h_mm[2] = {~0ull, 0ull};
+  hipError_t e = hipMemcpy(d_mm, init, 16, hipMemcpyHostToDevice);
+  if (e == hipSuccess && tab->rows) {
+    const uint32_t nb =
+      (uint32_t)std::min<uint64_t>(2048, (tab->rows + 255) / 256);
+    hipLaunchKernelGGL(col_minmax_valid_kernel, dim3(nb), dim3(256), 0,
+                       ctx->stream, tab->refs[col], tab->valid[col],
+                       tab->rows, tab->group_rows, d_mm);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  }
+  if (e == hipSuccess) e = hipMemcpy(h_mm, d_mm, 16, hipMemcpyDeviceToHost);
+  (void)hipFree(d_mm);
+  if (e != hipSuccess)
+    return e == hipErrorNoDevice ? SDB_ERR_NO_GPU : SDB_ERR_HIP;
+  tab->valid_min[col] = (int64_t)(h_mm[0] ^ 0x8000000000000000ull);
+  tab->valid_max[col] = (int64_t)(h_mm[1] ^ 0x8000000000000000ull);
+  tab->has_valid_minmax[col] = 1;
+  return SDB_OK;
+}
+
+// Dense scan shared by sdb_gpu_scan_agg (null_rows == nullptr: out holds
+// ngroups rows and a key plane is rejected) and sdb_gpu_scan_agg_nullkey
+// (out holds ngroups + 1 rows, the last one the NULL group).
+static int scan_agg_dense(SdbGpuCtx* ctx, SdbGpuTable* tab,
+                          uint32_t group_col, uint32_t ngroups,
+                          const SdbPredSpec* preds, uint32_t npreds,
+                          const SdbAggSpec* aggs, uint32_t naggs,
+                          SdbAggResult* out, uint64_t* rows_passed,
+                          uint64_t* null_rows) {
   if (!ctx || !tab || !out || !rows_passed || group_col >= tab->ncols ||
       ngroups == 0 || ngroups > SCAN_MAX_GROUPS || naggs == 0 ||
       naggs > SCAN_MAX_AGGS || npreds > SCAN_MAX_PREDS)
@@ -1587,19 +1762,34 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
   bool ext = false;
   if (agg_specs_check(tab, aggs, naggs, &ext)) return SDB_ERR_INVALID;
   if (tab->types[group_col] == SDB_COL_F32) return SDB_ERR_INVALID;
-  if (tab->valid[group_col]) return SDB_ERR_INVALID;  // no NULL groups
+  if (!null_rows && tab->valid[group_col])
+    return SDB_ERR_INVALID;  // NULL groups: sdb_gpu_scan_agg_nullkey
+  // nk: the NK = 1 instantiations run, with the NULL group as accumulator
+  // row ngroups. Without a key plane the nullable entry launches exactly
+  // what sdb_gpu_scan_agg launches and its NULL row decodes from zeros.
+  const bool nk = null_rows && tab->valid[group_col];
   // dense-key contract: keys must be provably inside [0, ngroups) or the
   // perfect-hash accumulate acc[key*naggs+q] corrupts LDS. Both column
   // kinds carry a load-time range (FoR zonemaps / raw-column reduction).
-  if (tab->rows && tab->has_minmax[group_col] &&
-      (tab->col_min[group_col] < 0 ||
-       tab->col_max[group_col] >= (int64_t)ngroups))
+  // Under a key plane the contract binds the valid rows alone, and the
+  // range is taken over them (valid_minmax); no valid row proves trivially.
+  if (nk) {
+    const int rc = valid_minmax(ctx, tab, group_col);
+    if (rc) return rc;
+    if (tab->valid_min[group_col] <= tab->valid_max[group_col] &&
+        (tab->valid_min[group_col] < 0 ||
+         tab->valid_max[group_col] >= (int64_t)ngroups))
+      return SDB_ERR_INVALID;
+  } else if (tab->rows && tab->has_minmax[group_col] &&
+             (tab->col_min[group_col] < 0 ||
+              tab->col_max[group_col] >= (int64_t)ngroups))
     return SDB_ERR_INVALID;
 
   hipStream_t stream = ctx->stream;
 
-  ScanArgs a{};
+  ScanArgsNK a{};  // the NK = 0 launches take its ScanArgs base
   a.keys = tab->refs[group_col];
+  a.key_valid = nk ? tab->valid[group_col] : nullptr;
   a.rows = tab->rows;
   a.group_rows = tab->group_rows;
   a.ngroups = ngroups;
@@ -1647,7 +1837,9 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
           a.agg_src[q] = 1 + (int)p;
     }
   }
-  const uint32_t nslots = ngroups * naggs;
+  // accumulator slots in LDS and in d_out; the staged-chunk sizing below
+  // works from this, i.e. from the table enlarged by the NULL row
+  const uint32_t nslots = (ngroups + (nk ? 1u : 0u)) * naggs;
   // ctx-cached workspace: the dense scan hot path allocates nothing per
   // call (grown on demand; buffers owned and freed by the context)
 #define HIP_CHECK_CLEAN(x)                                   \
@@ -1666,14 +1858,15 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
     HIP_CHECK_CLEAN(hipMalloc(&ctx->d_scan_out, 8ull * nslots));
     ctx->scan_out_cap = nslots;
   }
-  if (!ctx->d_scan_passed)
-    HIP_CHECK_CLEAN(hipMalloc(&ctx->d_scan_passed, 8));
+  if (!ctx->d_scan_passed)  // [0] rows passed, [1] NULL-key rows passed
+    HIP_CHECK_CLEAN(hipMalloc(&ctx->d_scan_passed, 16));
   unsigned long long* d_out = ctx->d_scan_out;
   unsigned long long* d_passed = ctx->d_scan_passed;
   HIP_CHECK_CLEAN(hipMemsetAsync(d_out, 0, 8ull * nslots, stream));
-  HIP_CHECK_CLEAN(hipMemsetAsync(d_passed, 0, 8, stream));
+  HIP_CHECK_CLEAN(hipMemsetAsync(d_passed, 0, 16, stream));
   a.out = d_out;
   a.rows_passed = d_passed;
+  a.null_rows = d_passed + 1;
 
   uint32_t nblocks =
     (uint32_t)((tab->rows + a.group_rows - 1) / a.group_rows);
@@ -1753,7 +1946,19 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
   // >= SDB_AGG_COUNT_COL: lists of the three original ops launch
   // instantiations whose per-row switch has no arm for the new ones (a
   // shape3 list never has one, so ASHAPE = 1 exists with EXT = 0 only).
-  if (staged && shape3)
+  // A key plane (nk) launches the NK = 1 instantiations, which exist for
+  // ASHAPE = 0, EXT = 1 only — EXT = 1 handles every op, the old three
+  // included: one each for staged, FoR and raw.
+  if (nk && staged)
+    hipLaunchKernelGGL((scan_agg_staged_kernel<0, 1, 1>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
+  else if (nk && any_for)
+    hipLaunchKernelGGL((scan_agg_kernel<0, 0, 1, 1>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
+  else if (nk)
+    hipLaunchKernelGGL((scan_agg_kernel<1, 0, 1, 1>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
+  else if (staged && shape3)
     hipLaunchKernelGGL((scan_agg_staged_kernel<1, 0>), dim3(nblocks),
                        dim3(SCAN_NTHREADS), lds, stream, a);
   else if (staged && ext)
@@ -1783,10 +1988,10 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
                        dim3(SCAN_NTHREADS), lds, stream, a);
   HIP_CHECK_CLEAN(hipGetLastError());
   std::vector<unsigned long long> h_out(nslots);
-  unsigned long long h_passed = 0;
+  unsigned long long h_passed[2] = {0, 0};
   HIP_CHECK_CLEAN(hipMemcpyAsync(h_out.data(), d_out, 8ull * nslots,
                                  hipMemcpyDeviceToHost, stream));
-  HIP_CHECK_CLEAN(hipMemcpyAsync(&h_passed, d_passed, 8,
+  HIP_CHECK_CLEAN(hipMemcpyAsync(h_passed, d_passed, 16,
                                  hipMemcpyDeviceToHost, stream));
   HIP_CHECK_CLEAN(hipStreamSynchronize(stream));
 #undef HIP_CHECK_CLEAN
@@ -1795,8 +2000,33 @@ int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
     for (uint32_t q = 0; q < naggs; ++q)
       agg_decode(aggs[q].op, h_out[g * naggs + q], &out[g * naggs + q]);
   }
-  *rows_passed = h_passed;
+  if (null_rows) {  // row ngroups: the NULL group (zeros without a plane)
+    for (uint32_t q = 0; q < naggs; ++q)
+      agg_decode(aggs[q].op, nk ? h_out[ngroups * naggs + q] : 0ull,
+                 &out[ngroups * naggs + q]);
+    *null_rows = nk ? h_passed[1] : 0;
+  }
+  *rows_passed = h_passed[0];
   return SDB_OK;
+}
+
+int sdb_gpu_scan_agg(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t group_col,
+                     uint32_t ngroups, const SdbPredSpec* preds,
+                     uint32_t npreds, const SdbAggSpec* aggs, uint32_t naggs,
+                     SdbAggResult* out, uint64_t* rows_passed) {
+  return scan_agg_dense(ctx, tab, group_col, ngroups, preds, npreds, aggs,
+                        naggs, out, rows_passed, nullptr);
+}
+
+int sdb_gpu_scan_agg_nullkey(SdbGpuCtx* ctx, SdbGpuTable* tab,
+                             uint32_t group_col, uint32_t ngroups,
+                             const SdbPredSpec* preds, uint32_t npreds,
+                             const SdbAggSpec* aggs, uint32_t naggs,
+                             SdbAggResult* out, uint64_t* rows_passed,
+                             uint64_t* null_rows) {
+  if (!null_rows) return SDB_ERR_INVALID;
+  return scan_agg_dense(ctx, tab, group_col, ngroups, preds, npreds, aggs,
+                        naggs, out, rows_passed, null_rows);
 }
 
 
@@ -1808,7 +2038,12 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
                               const SdbAggSpec* aggs, uint32_t naggs,
                               int64_t* keys_out, SdbAggResult* out,
                               uint64_t* ngroups_out,
-                              uint64_t* rows_passed) {
+                              uint64_t* rows_passed,
+                              const unsigned long long* key_valid = nullptr,
+                              SdbAggResult* null_out = nullptr,
+                              uint64_t* null_rows = nullptr) {
+  // key_valid: the key column's own plane (sdb_gpu_scan_agg_hash_nullkey
+  // only): launches the NK = 1 instantiation and fills null_out/null_rows
   if (!ctx || !tab || !keys_out || !out || !ngroups_out || !rows_passed ||
       max_groups == 0 || max_groups > (1u << 22) || naggs == 0 ||
       naggs > SCAN_MAX_AGGS || npreds > SCAN_MAX_PREDS)
@@ -1817,7 +2052,7 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
   if (agg_specs_check(tab, aggs, naggs, &ext)) return SDB_ERR_INVALID;
 
   hipStream_t stream = ctx->stream;
-  HashAggArgs a{};
+  HashAggArgsNK a{};  // the NK = 0 launches take its HashAggArgs base
   a.keys = gkeys;
   a.rows = tab->rows;
   a.group_rows = tab->group_rows;
@@ -1871,13 +2106,17 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
     slots >>= 1;
   if (max_groups > (uint64_t)slots * 2) slots = 0;
   a.lds_slots = slots;
-  const size_t lds = slots ? (size_t)slots * 8 * (1 + naggs) : 16;
+  a.key_valid = key_valid;
+  // NK = 1 keeps the workgroup's NULL-group accumulators past the table
+  const size_t lds = std::max<size_t>(
+    (size_t)slots * 8 * (1 + naggs) + (key_valid ? 8 * naggs : 0), 16);
 
   unsigned long long* d_keys = nullptr;
   unsigned long long* d_acc = nullptr;
   unsigned long long* d_misc = nullptr;  // [0]=inserts|overflow, then
-                                         // neg_acc[naggs+1], rows_passed
-  const size_t misc_words = 1 + (naggs + 1) + 1;
+                                         // neg_acc[naggs+1], rows_passed,
+                                         // null_acc[naggs+1]
+  const size_t misc_words = 1 + (naggs + 1) + 1 + (naggs + 1);
 #define HASH_CHECK(x)                                        \
   do {                                                       \
     hipError_t _e = (x);                                     \
@@ -1902,12 +2141,16 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
   a.goverflow = (uint32_t*)d_misc + 1;
   a.neg_acc = d_misc + 1;
   a.rows_passed = d_misc + 1 + (naggs + 1);
+  a.null_acc = d_misc + 1 + (naggs + 1) + 1;
 
   uint32_t nblocks =
     (uint32_t)((tab->rows + a.group_rows - 1) / a.group_rows);
   if (nblocks > SCAN_MAXB) nblocks = SCAN_MAXB;
   if (nblocks < 1) nblocks = 1;
-  if (ext)  // as in sdb_gpu_scan_agg: old-op lists keep the old switch
+  if (key_valid)  // the one NK = 1 instantiation: EXT = 1 handles every op
+    hipLaunchKernelGGL((scan_agg_hash_kernel<1, 1>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
+  else if (ext)  // as in sdb_gpu_scan_agg: old-op lists keep the old switch
     hipLaunchKernelGGL((scan_agg_hash_kernel<1>), dim3(nblocks),
                        dim3(SCAN_NTHREADS), lds, stream, a);
   else
@@ -1962,6 +2205,12 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
     emit((int64_t)h_keys[live[li]], &h_acc[(uint64_t)live[li] * naggs]);
   *ngroups_out = n;
   *rows_passed = h_misc[1 + naggs + 1];
+  // the NULL group: outside the key groups, no share of max_groups; all
+  // zeros (identities once decoded) when no NULL-key row passed
+  if (null_out)
+    for (uint32_t q = 0; q < naggs; ++q)
+      agg_decode(aggs[q].op, h_misc[1 + (naggs + 1) + 1 + q], &null_out[q]);
+  if (null_rows) *null_rows = h_misc[1 + (naggs + 1) + 1 + naggs];
   return SDB_OK;
 }
 
@@ -1973,10 +2222,30 @@ int sdb_gpu_scan_agg_hash(SdbGpuCtx* ctx, SdbGpuTable* tab,
                           uint64_t* ngroups_out, uint64_t* rows_passed) {
   if (!ctx || !tab || group_col >= tab->ncols) return SDB_ERR_INVALID;
   if (tab->types[group_col] == SDB_COL_F32) return SDB_ERR_INVALID;
-  if (tab->valid[group_col]) return SDB_ERR_INVALID;  // no NULL groups
+  if (tab->valid[group_col])
+    return SDB_ERR_INVALID;  // NULL groups: sdb_gpu_scan_agg_hash_nullkey
   return scan_agg_hash_core(ctx, tab, tab->refs[group_col], max_groups,
                             preds, npreds, aggs, naggs, keys_out, out,
                             ngroups_out, rows_passed);
+}
+
+int sdb_gpu_scan_agg_hash_nullkey(SdbGpuCtx* ctx, SdbGpuTable* tab,
+                                  uint32_t group_col, uint64_t max_groups,
+                                  const SdbPredSpec* preds, uint32_t npreds,
+                                  const SdbAggSpec* aggs, uint32_t naggs,
+                                  int64_t* keys_out, SdbAggResult* out,
+                                  uint64_t* ngroups_out,
+                                  uint64_t* rows_passed,
+                                  SdbAggResult* null_out,
+                                  uint64_t* null_rows) {
+  if (!ctx || !tab || group_col >= tab->ncols || !null_out || !null_rows)
+    return SDB_ERR_INVALID;
+  if (tab->types[group_col] == SDB_COL_F32) return SDB_ERR_INVALID;
+  // no plane: key_valid is null and the old instantiations run
+  return scan_agg_hash_core(ctx, tab, tab->refs[group_col], max_groups,
+                            preds, npreds, aggs, naggs, keys_out, out,
+                            ngroups_out, rows_passed, tab->valid[group_col],
+                            null_out, null_rows);
 }
 
 // FNV-1a 64 over each row's DECODED string bytes (raw slot: the bytes
