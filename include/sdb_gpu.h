@@ -50,6 +50,7 @@ extern "C" {
 #define SDB_ERR_HIP (-3)
 #define SDB_ERR_OOM (-4)
 #define SDB_ERR_BAD_SEGMENT (-5)
+#define SDB_ERR_COLLISION (-6) /* sdb_gpu_scan_agg_hash_multi: see there */
 
 /* mirrors irs::ScoreDoc: {score_t score; doc_id_t doc; uint32_t segment_idx}
  * (index/iterators.hpp:93-99) */
@@ -486,6 +487,72 @@ int sdb_gpu_scan_agg_hash_nullkey(SdbGpuCtx* ctx, SdbGpuTable* tab,
                                   uint64_t* rows_passed,
                                   SdbAggResult* null_out /* naggs */,
                                   uint64_t* null_rows);
+
+#define SDB_MAX_GROUP_KEYS 4
+
+/* ---- GROUP BY several key columns ----
+ * The hash aggregate over a COMPOSITE key: 1..SDB_MAX_GROUP_KEYS columns,
+ * each I64 or I64_FOR, each with or without a validity plane (F32 is
+ * rejected; a repeated column is allowed and harmless). nkeys == 0, nkeys >
+ * SDB_MAX_GROUP_KEYS, a column index >= ncols and every bad aggregate /
+ * predicate case of the entries above return SDB_ERR_INVALID before
+ * anything is launched.
+ *
+ * Group identity: a group is a distinct tuple, and in each position NULL is
+ * a value of its own, equal only to NULL (SQL GROUP BY, and what the DuckDB
+ * consumer does). The stored key of a NULL position is never an input: it
+ * may be -1, an int64 extreme or a live key. Every distinct tuple counts
+ * against max_groups, tuples with NULLs included — unlike
+ * sdb_gpu_scan_agg_hash_nullkey, whose single NULL group is kept apart.
+ * More tuples than max_groups (<= 4M) returns SDB_ERR_OOM. Predicates and
+ * aggregates over a key column keep their meaning: a compare drops that
+ * column's NULL rows, ISNULL / NOTNULL read its plane, STRMASK works as
+ * above, and SUM / MIN / MAX / COUNT_COL over a key skip its NULL rows.
+ *
+ * Result order: tuples ascending, compared column by column as signed
+ * int64, NULL last in its column. keys_out row n holds the nkeys values of
+ * group n (0 in a NULL position), keynull_out[n] has bit j set when key j of
+ * the group is NULL.
+ *
+ * How it is exact. No tuple is stored on the device and no thread waits
+ * for another. Each passing row hashes its tuple to 64 bits,
+ *   h = mix64(seed + 1)
+ *   for j in 0..nkeys-1:  h = mix64(h ^ (null_j ? 0 : (uint64)key_j))
+ *   h = mix64(h ^ nullmask)            bit j of nullmask = null_j
+ *   h &= hash_mask                     all ones unless the hook below is set
+ *   if (h == 2^64 - 1) h -= 1          the tables' empty marker
+ * with mix64 the splitmix64 finaliser (x ^= x >> 30; x *= 0xbf58476d1ce4e5b9;
+ * x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31), and upserts h into
+ * the open-addressed tables of sdb_gpu_scan_agg_hash. Beside its naggs
+ * accumulators every slot carries 2*nkeys + 2 witness words: per key the MIN
+ * and the MAX of that key over the slot's rows where it is valid, plus the
+ * bitwise OR and the bitwise AND of the rows' null masks. On readback the
+ * host proves each slot: it holds exactly one tuple iff OR == AND and
+ * min_j == max_j in every position not NULL, and the tuple is then (min_j)
+ * with the mask. The proof is complete — two different tuples differ in
+ * some position, in null-ness (OR != AND) or in value (min != max).
+ *
+ * If any slot fails the proof the whole scan repeats with the next seed, 0
+ * through 3; if all four fail the call returns SDB_ERR_COLLISION. A wrong
+ * answer is never returned. At 64 bits and 4M groups one seed collides with
+ * probability about 5e-7, so callers do not see the error in practice.
+ *
+ * Test hook: the environment variable SDB_MK_HASH_BITS (1..64, read per
+ * call) sets hash_mask = 2^bits - 1, so that the witness and the retry can
+ * be exercised. Not for production use.
+ *
+ * Allocates / frees its device workspace per call, as the hash entries do. */
+int sdb_gpu_scan_agg_hash_multi(SdbGpuCtx* ctx, SdbGpuTable* tab,
+                                const uint32_t* group_cols,
+                                uint32_t nkeys /* 1..SDB_MAX_GROUP_KEYS */,
+                                uint64_t max_groups,
+                                const SdbPredSpec* preds, uint32_t npreds,
+                                const SdbAggSpec* aggs, uint32_t naggs,
+                                int64_t* keys_out /* max_groups*nkeys */,
+                                uint32_t* keynull_out /* max_groups */,
+                                SdbAggResult* out /* max_groups*naggs */,
+                                uint64_t* ngroups_out,
+                                uint64_t* rows_passed);
 
 /* GROUP BY string keys over an attached raw or FSST string slot (the
  * reference hands text group-by to its DuckDB fork's hash aggregate —

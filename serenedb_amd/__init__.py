@@ -1051,6 +1051,45 @@ class GpuContext:
         return (keys_out[:n], i64, f64, passed.value, ni64[0], nf64[0],
                 nulls.value)
 
+    # ---- GROUP BY several key columns ----
+
+    def scan_agg_hash_multi(self, tab, group_cols, max_groups, preds, aggs):
+        """Hash aggregate over a composite key: group_cols names 1 to 4
+        i64 / FoR columns, each with or without a validity plane. A group
+        is a distinct tuple; NULL in a position is a value of its own, and
+        every tuple — those with NULLs too — counts against max_groups.
+        preds / aggs as in scan_agg. Returns (keys int64 [n, nkeys],
+        keynull bool [n, nkeys], i64 [n, naggs], f64 [n, naggs],
+        rows_passed): tuples ascending column by column, NULL last in its
+        column; keys holds 0 where keynull is set. Exact: the device groups
+        by a 64-bit hash of the tuple and every group is proved to hold one
+        tuple before it is returned (rc=-6, SDB_ERR_COLLISION, if four
+        seeds in a row fail that proof)."""
+        import numpy as np
+
+        nk = len(group_cols)
+        na = len(aggs)
+        gc = (C.c_uint32 * max(nk, 1))(*group_cols)
+        keys_out = np.zeros((max_groups, max(nk, 1)), dtype=np.int64)
+        null_out = np.zeros(max_groups, dtype=np.uint32)
+        out = (self._AggResult * (max_groups * max(na, 1)))()
+        ng = C.c_uint64(0)
+        passed = C.c_uint64(0)
+        rc = self._lib.sdb_gpu_scan_agg_hash_multi(
+            self._ctx, tab, gc, C.c_uint32(nk), C.c_uint64(max_groups),
+            self._pred_specs(preds), C.c_uint32(len(preds)),
+            self._agg_specs(aggs), C.c_uint32(na),
+            keys_out.ctypes.data_as(C.POINTER(C.c_int64)),
+            null_out.ctypes.data_as(C.POINTER(C.c_uint32)), out,
+            C.byref(ng), C.byref(passed))
+        if rc != 0:
+            raise RuntimeError(f"sdb_gpu_scan_agg_hash_multi rc={rc}")
+        n = ng.value
+        i64, f64 = self._unpack_aggs(out, n, na)
+        keys = keys_out[:n]
+        keynull = (null_out[:n, None] >> np.arange(nk, dtype=np.uint32)) & 1
+        return keys, keynull.astype(bool), i64, f64, passed.value
+
 
     def execute_topk_batch(self, segs, term_idx, boosts, k, nq,
                            min_match=1, k1=1.2, b=0.75, global_stats=None,

@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -1235,6 +1236,237 @@ void scan_agg_hash_kernel(typename HashAggArgsOf<NK>::type a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Composite group key: GROUP BY 1..SDB_MAX_GROUP_KEYS nullable i64 columns.
+// A tuple does not fit the 64-bit key the tables CAS, and a wider key would
+// need a thread to wait for another's publish — a spin inside a divergent
+// wave. So the tables keep what they key on today, one u64: a 64-bit hash of
+// the row's tuple, computed in registers (tuple_hash). What makes the answer
+// exact is carried NEXT TO the accumulators: every slot, in LDS and in the
+// global table, ends in 2*nkeys + 2 witness words —
+//   [naggs + 2j]     MIN of key j over the slot's rows where key j is valid
+//   [naggs + 2j + 1] MAX of the same; both as agg_row's "bigger wins" codes
+//   [naggs + 2*nkeys]      OR of the rows' null masks (bit j = key j NULL)
+//   [naggs + 2*nkeys + 1]  OR of their complements (the AND, zero-initialised)
+// The host reads them back: a slot holds ONE tuple iff the two masks are
+// disjoint and min_j == max_j in every position not NULL, and that tuple is
+// then (min_j) with the mask. Two different tuples differ in some position,
+// in null-ness (the masks overlap) or in value (min != max), so the check is
+// complete; a slot that fails it makes the host run the scan again under the
+// next seed. No thread ever waits for another.
+// ---------------------------------------------------------------------------
+
+// argument of the composite-key kernel; the other instantiations keep their
+// own structs (see ScanArgsNK)
+struct HashAggArgsMK : HashAggArgs {
+  uint32_t nkeys;                    // 1..SDB_MAX_GROUP_KEYS
+  uint32_t stride;                   // words per slot: naggs + 2*nkeys + 2
+  ColRef mkeys[SDB_MAX_GROUP_KEYS];
+  const unsigned long long* key_valid[SDB_MAX_GROUP_KEYS];  // null = no plane
+  uint64_t seed;                     // 0..3, one per attempt
+  uint64_t hash_mask;                // all ones unless SDB_MK_HASH_BITS
+};
+
+// The hash of a tuple (include/sdb_gpu.h states it; the tests restate it).
+// A NULL position contributes 0, whatever the row stores there.
+__device__ __forceinline__ uint64_t tuple_hash(
+  const HashAggArgsMK& a, const int64_t (&key)[SDB_MAX_GROUP_KEYS],
+  uint32_t nullmask) {
+  uint64_t h = mix64(a.seed + 1);
+#pragma unroll
+  for (uint32_t j = 0; j < SDB_MAX_GROUP_KEYS; ++j)
+    if (j < a.nkeys)
+      h = mix64(h ^ (((nullmask >> j) & 1u) ? 0ull : (uint64_t)key[j]));
+  h = mix64(h ^ (uint64_t)nullmask);
+  h &= a.hash_mask;
+  if (h == SDB_HKEY_EMPTY) h -= 1;  // the empty marker is no hash
+  return h;
+}
+
+// One row's tuple into the witness words of its slot. In LDS (GLOBAL = 0)
+// the words take the row as the accumulators do, one no-return atomic each.
+// In the global table every atomic is a trip to L2, so there each word is
+// read first and the atomic issued only if it would change the word: every
+// word only ever grows (a max, or an OR), and from a slot's second row on it
+// already holds what the row would write unless two tuples share the slot.
+// A stale read can only cost a redundant atomic, never lose one.
+template <int GLOBAL>
+__device__ __forceinline__ bool witness_has(const unsigned long long* p,
+                                            unsigned long long v,
+                                            bool is_or) {
+  if (!GLOBAL) return false;
+  const unsigned long long cur =
+    __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return is_or ? (v & ~cur) == 0 : cur >= v;
+}
+
+template <int GLOBAL>
+__device__ __forceinline__ void witness_row(
+  unsigned long long* w, uint32_t nkeys,
+  const int64_t (&key)[SDB_MAX_GROUP_KEYS], uint32_t nullmask) {
+#pragma unroll
+  for (uint32_t j = 0; j < SDB_MAX_GROUP_KEYS; ++j)
+    if (j < nkeys && !((nullmask >> j) & 1u)) {
+      const unsigned long long c = (unsigned long long)key[j] ^ SDB_I64_SIGN;
+      if (!witness_has<GLOBAL>(&w[2 * j], ~c, false))
+        atomicMax(&w[2 * j], ~c);
+      if (!witness_has<GLOBAL>(&w[2 * j + 1], c, false))
+        atomicMax(&w[2 * j + 1], c);
+    }
+  const unsigned long long nm = nullmask;
+  const unsigned long long comp = ~nullmask & ((1u << nkeys) - 1u);
+  if (nm && !witness_has<GLOBAL>(&w[2 * nkeys], nm, true))
+    atomicOr(&w[2 * nkeys], nm);
+  if (comp && !witness_has<GLOBAL>(&w[2 * nkeys + 1], comp, true))
+    atomicOr(&w[2 * nkeys + 1], comp);
+}
+
+// The live slots of the global table, accumulators and witness words, packed
+// into out[max_out * stride] in no particular order (the host sorts): the
+// readback is then the groups found, not the whole half-empty table. *nout
+// counts every live slot; slots past max_out are dropped, and the host has
+// by then answered SDB_ERR_OOM from the insert count.
+__global__ void hash_multi_compact_kernel(
+  const unsigned long long* __restrict__ gkeys,
+  const unsigned long long* __restrict__ gacc, uint32_t cap, uint32_t stride,
+  uint32_t max_out, unsigned long long* __restrict__ out, uint32_t* nout) {
+  const uint32_t step = gridDim.x * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < cap;
+       i += step) {
+    if (gkeys[i] == SDB_HKEY_EMPTY) continue;
+    const uint32_t at = atomicAdd(nout, 1u);
+    if (at >= max_out) continue;
+    for (uint32_t w = 0; w < stride; ++w)
+      out[(uint64_t)at * stride + w] = gacc[(uint64_t)i * stride + w];
+  }
+}
+
+__launch_bounds__(SCAN_NTHREADS) __global__
+void scan_agg_hash_multi_kernel(HashAggArgsMK a) {
+  constexpr int EXT = 1;  // one instantiation: EXT = 1 handles every op
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* lkey = (unsigned long long*)smem;  // lds_slots
+  unsigned long long* lacc = lkey + a.lds_slots;         // slots*stride
+  const uint32_t S_mask = a.lds_slots ? a.lds_slots - 1 : 0;
+  for (uint32_t i = threadIdx.x; i < a.lds_slots * (1 + a.stride);
+       i += SCAN_NTHREADS)
+    lkey[i] = i < a.lds_slots ? SDB_HKEY_EMPTY : 0ull;
+  __syncthreads();
+
+  const uint32_t n_rowgroups =
+    (uint32_t)((a.rows + a.group_rows - 1) / a.group_rows);
+  unsigned long long my_passed = 0;
+
+  for (uint32_t rg = blockIdx.x; rg < n_rowgroups; rg += gridDim.x) {
+    const uint64_t r0 = (uint64_t)rg * a.group_rows;
+    const uint64_t r1 = min(a.rows, r0 + a.group_rows);
+    bool dead = false;
+    for (uint32_t p = 0; p < a.npreds; ++p) {
+      if (a.pred_col[p].desc && !a.pred_isf32[p]) {
+        const SdbColGroupDescDev& d = a.pred_col[p].desc[rg];
+        switch (a.pred_op[p]) {
+          case SDB_PRED_LT: dead |= d.vmin >= a.pred_lo[p]; break;
+          case SDB_PRED_GE: dead |= d.vmax < a.pred_lo[p]; break;
+          case SDB_PRED_BETWEEN:
+            dead |= (d.vmax < a.pred_lo[p]) | (d.vmin > a.pred_hi[p]);
+            break;
+          case SDB_PRED_EQ:
+            dead |= (d.vmax < a.pred_lo[p]) | (d.vmin > a.pred_lo[p]);
+            break;
+          default: break;
+        }
+      }
+    }
+    if (dead) continue;
+
+    for (uint64_t r = r0 + threadIdx.x; r < r1; r += SCAN_NTHREADS) {
+      bool ok = true;
+      for (uint32_t p = 0; p < a.npreds; ++p) {
+        if (a.pred_isf32[p])
+          ok &= pred_eval_fv(a.pred_op[p], a.pred_valid[p], r,
+                             ((const float*)a.pred_col[p].data)[r],
+                             a.pred_flo[p], a.pred_fhi[p]);
+        else
+          ok &= pred_eval_iv(a.pred_op[p], a.pred_valid[p], r,
+                             col_read(a.pred_col[p], rg, r0, r),
+                             a.pred_lo[p], a.pred_hi[p]);
+      }
+      if (!ok) continue;
+      ++my_passed;
+      // the tuple in registers: a NULL position's stored value is read (the
+      // row is in bounds) and discarded by tuple_hash / witness_row
+      int64_t key[SDB_MAX_GROUP_KEYS];
+      uint32_t nullmask = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < SDB_MAX_GROUP_KEYS; ++j) {
+        key[j] = 0;
+        if (j < a.nkeys) {
+          key[j] = col_read(a.mkeys[j], rg, r0, r);
+          if (!valid_at(a.key_valid[j], r)) nullmask |= 1u << j;
+        }
+      }
+      const uint64_t k = tuple_hash(a, key, nullmask);
+      // LDS open-addressed probe (bounded), then global fallback
+      int slot = -1;
+      if (a.lds_slots) {
+        uint32_t h = (uint32_t)mix64(k) & S_mask;
+        for (uint32_t i = 0; i < 32; ++i) {
+          const unsigned long long cur = lkey[h];
+          if (cur == k) {
+            slot = (int)h;
+            break;
+          }
+          if (cur == SDB_HKEY_EMPTY) {
+            const unsigned long long prev =
+              atomicCAS(&lkey[h], SDB_HKEY_EMPTY, k);
+            if (prev == SDB_HKEY_EMPTY || prev == k) {
+              slot = (int)h;
+              break;
+            }
+          }
+          h = (h + 1) & S_mask;
+        }
+      }
+      // two arms, so that each knows its address space (LDS / global)
+      if (slot >= 0) {
+        unsigned long long* acc = &lacc[(uint32_t)slot * a.stride];
+        for (uint32_t q = 0; q < a.naggs; ++q)
+          hash_acc_add<EXT>(a, acc, q, rg, r0, r, false);
+        witness_row<0>(acc + a.naggs, a.nkeys, key, nullmask);
+      } else {
+        const int64_t g = hash_global_upsert(a, k);
+        if (g < 0) return;  // table overflow: host reports SDB_ERR_OOM
+        unsigned long long* acc = &a.gacc[(uint64_t)g * a.stride];
+        for (uint32_t q = 0; q < a.naggs; ++q)
+          hash_acc_add<EXT>(a, acc, q, rg, r0, r, true);
+        witness_row<1>(acc + a.naggs, a.nkeys, key, nullmask);
+      }
+    }
+  }
+
+  unsigned long long wp = my_passed;
+#pragma unroll
+  for (int off = 32; off; off >>= 1) wp += __shfl_down(wp, off, 64);
+  if ((threadIdx.x & 63) == 0 && wp) atomicAdd(a.rows_passed, wp);
+  __syncthreads();
+  // flush the LDS table into the global table: aggregates as agg_merge has
+  // them, min/max witness codes by max, the two masks by OR
+  for (uint32_t i = threadIdx.x; i < a.lds_slots; i += SCAN_NTHREADS) {
+    const unsigned long long k = lkey[i];
+    if (k == SDB_HKEY_EMPTY) continue;
+    const int64_t g = hash_global_upsert(a, k);
+    if (g < 0) return;
+    const unsigned long long* src = &lacc[i * a.stride];
+    unsigned long long* dst = &a.gacc[(uint64_t)g * a.stride];
+    for (uint32_t q = 0; q < a.naggs; ++q)
+      agg_merge<EXT>(&dst[q], a.agg_op[q], src[q]);
+    for (uint32_t w = a.naggs; w < a.naggs + 2 * a.nkeys; ++w)
+      if (src[w]) atomicMax(&dst[w], src[w]);
+    for (uint32_t w = a.naggs + 2 * a.nkeys; w < a.stride; ++w)
+      if (src[w]) atomicOr(&dst[w], src[w]);
+  }
+}
+
 extern "C" {
 
 static void table_free_str(SdbGpuTable* tab) {
@@ -2030,29 +2262,13 @@ int sdb_gpu_scan_agg_nullkey(SdbGpuCtx* ctx, SdbGpuTable* tab,
 }
 
 
-// core shared by the i64-key entry and the string-key entry: gkeys is
-// the group-key column (a table column or a derived device array)
-static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
-                              ColRef gkeys, uint64_t max_groups,
-                              const SdbPredSpec* preds, uint32_t npreds,
-                              const SdbAggSpec* aggs, uint32_t naggs,
-                              int64_t* keys_out, SdbAggResult* out,
-                              uint64_t* ngroups_out,
-                              uint64_t* rows_passed,
-                              const unsigned long long* key_valid = nullptr,
-                              SdbAggResult* null_out = nullptr,
-                              uint64_t* null_rows = nullptr) {
-  // key_valid: the key column's own plane (sdb_gpu_scan_agg_hash_nullkey
-  // only): launches the NK = 1 instantiation and fills null_out/null_rows
-  if (!ctx || !tab || !keys_out || !out || !ngroups_out || !rows_passed ||
-      max_groups == 0 || max_groups > (1u << 22) || naggs == 0 ||
-      naggs > SCAN_MAX_AGGS || npreds > SCAN_MAX_PREDS)
-    return SDB_ERR_INVALID;
-  bool ext = false;
-  if (agg_specs_check(tab, aggs, naggs, &ext)) return SDB_ERR_INVALID;
-
-  hipStream_t stream = ctx->stream;
-  HashAggArgsNK a{};  // the NK = 0 launches take its HashAggArgs base
+// The scan description every hash-aggregate kernel shares: the predicate
+// and aggregate lists resolved against the table. gkeys is the value column a
+// STRMASK predicate rides on. Run before anything is allocated or launched.
+static int hash_args_fill(HashAggArgs& a, const SdbGpuTable* tab,
+                          ColRef gkeys, const SdbPredSpec* preds,
+                          uint32_t npreds, const SdbAggSpec* aggs,
+                          uint32_t naggs) {
   a.keys = gkeys;
   a.rows = tab->rows;
   a.group_rows = tab->group_rows;
@@ -2091,6 +2307,34 @@ static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
     a.agg_valid[q] =
       aggs[q].op == SDB_AGG_COUNT ? nullptr : tab->valid[aggs[q].col];
   }
+  return SDB_OK;
+}
+
+// core shared by the i64-key entry and the string-key entry: gkeys is
+// the group-key column (a table column or a derived device array)
+static int scan_agg_hash_core(SdbGpuCtx* ctx, SdbGpuTable* tab,
+                              ColRef gkeys, uint64_t max_groups,
+                              const SdbPredSpec* preds, uint32_t npreds,
+                              const SdbAggSpec* aggs, uint32_t naggs,
+                              int64_t* keys_out, SdbAggResult* out,
+                              uint64_t* ngroups_out,
+                              uint64_t* rows_passed,
+                              const unsigned long long* key_valid = nullptr,
+                              SdbAggResult* null_out = nullptr,
+                              uint64_t* null_rows = nullptr) {
+  // key_valid: the key column's own plane (sdb_gpu_scan_agg_hash_nullkey
+  // only): launches the NK = 1 instantiation and fills null_out/null_rows
+  if (!ctx || !tab || !keys_out || !out || !ngroups_out || !rows_passed ||
+      max_groups == 0 || max_groups > (1u << 22) || naggs == 0 ||
+      naggs > SCAN_MAX_AGGS || npreds > SCAN_MAX_PREDS)
+    return SDB_ERR_INVALID;
+  bool ext = false;
+  if (agg_specs_check(tab, aggs, naggs, &ext)) return SDB_ERR_INVALID;
+
+  hipStream_t stream = ctx->stream;
+  HashAggArgsNK a{};  // the NK = 0 launches take its HashAggArgs base
+  if (hash_args_fill(a, tab, gkeys, preds, npreds, aggs, naggs))
+    return SDB_ERR_INVALID;
   // global table: pow2 capacity >= 2*max_groups (load factor <= 0.5)
   uint64_t cap = 64;
   while (cap < 2 * max_groups) cap <<= 1;
@@ -2246,6 +2490,188 @@ int sdb_gpu_scan_agg_hash_nullkey(SdbGpuCtx* ctx, SdbGpuTable* tab,
                             preds, npreds, aggs, naggs, keys_out, out,
                             ngroups_out, rows_passed, tab->valid[group_col],
                             null_out, null_rows);
+}
+
+// GROUP BY 1..SDB_MAX_GROUP_KEYS nullable i64 columns (include/sdb_gpu.h;
+// the scheme is described at scan_agg_hash_multi_kernel). One scan per seed;
+// the host proves every slot from its witness words before it returns one.
+int sdb_gpu_scan_agg_hash_multi(SdbGpuCtx* ctx, SdbGpuTable* tab,
+                                const uint32_t* group_cols, uint32_t nkeys,
+                                uint64_t max_groups,
+                                const SdbPredSpec* preds, uint32_t npreds,
+                                const SdbAggSpec* aggs, uint32_t naggs,
+                                int64_t* keys_out, uint32_t* keynull_out,
+                                SdbAggResult* out, uint64_t* ngroups_out,
+                                uint64_t* rows_passed) {
+  if (!ctx || !tab || !group_cols || !keys_out || !keynull_out || !out ||
+      !ngroups_out || !rows_passed || nkeys == 0 ||
+      nkeys > SDB_MAX_GROUP_KEYS || max_groups == 0 ||
+      max_groups > (1u << 22) || naggs == 0 || naggs > SCAN_MAX_AGGS ||
+      npreds > SCAN_MAX_PREDS)
+    return SDB_ERR_INVALID;
+  for (uint32_t j = 0; j < nkeys; ++j)
+    if (group_cols[j] >= tab->ncols ||
+        tab->types[group_cols[j]] == SDB_COL_F32)
+      return SDB_ERR_INVALID;
+  bool ext = false;
+  if (agg_specs_check(tab, aggs, naggs, &ext)) return SDB_ERR_INVALID;
+
+  hipStream_t stream = ctx->stream;
+  HashAggArgsMK a{};
+  if (hash_args_fill(a, tab, tab->refs[group_cols[0]], preds, npreds, aggs,
+                     naggs))
+    return SDB_ERR_INVALID;
+  a.nkeys = nkeys;
+  a.stride = naggs + 2 * nkeys + 2;
+  for (uint32_t j = 0; j < nkeys; ++j) {
+    a.mkeys[j] = tab->refs[group_cols[j]];
+    a.key_valid[j] = tab->valid[group_cols[j]];
+  }
+  // test hook, read per call: keep only the low bits of the hash so that
+  // the witness check and the reseeded scan can be exercised
+  a.hash_mask = ~0ull;
+  if (const char* hb = getenv("SDB_MK_HASH_BITS")) {
+    const long bits = std::strtol(hb, nullptr, 10);
+    if (bits >= 1 && bits < 64) a.hash_mask = (1ull << bits) - 1;
+  }
+  const uint32_t stride = a.stride;
+  uint64_t cap = 64;  // pow2 capacity >= 2*max_groups, as scan_agg_hash_core
+  while (cap < 2 * max_groups) cap <<= 1;
+  a.gcap_mask = (uint32_t)(cap - 1);
+  a.max_groups = (uint32_t)max_groups;
+  // LDS: largest pow2 slot count whose (hash + accumulators + witness words)
+  // fit; off when the bound on distinct tuples dwarfs the table
+  uint32_t slots = 1u << 14;
+  while (slots && (uint64_t)slots * 8 * (1 + stride) > 150 * 1024)
+    slots >>= 1;
+  if (max_groups > (uint64_t)slots * 2) slots = 0;
+  a.lds_slots = slots;
+  const size_t lds = std::max<size_t>((size_t)slots * 8 * (1 + stride), 16);
+
+  // one allocation: [keys cap][acc cap*stride][misc 3][out max_groups*stride]
+  // misc: [0]=inserts|overflow, rows_passed, live slots packed; out: the
+  // live slots packed
+  unsigned long long* d_ws = nullptr;
+  const uint64_t acc_words = cap * stride;
+  auto release = [&] {
+    if (d_ws) (void)hipFree(d_ws);
+  };
+#define MK_CHECK(x)                                          \
+  do {                                                       \
+    hipError_t _e = (x);                                     \
+    if (_e != hipSuccess) {                                  \
+      release();                                             \
+      return _e == hipErrorNoDevice ? SDB_ERR_NO_GPU         \
+             : _e == hipErrorOutOfMemory ? SDB_ERR_OOM       \
+                                         : SDB_ERR_HIP;      \
+    }                                                        \
+  } while (0)
+  MK_CHECK(hipMalloc(
+    &d_ws, (cap + acc_words + 3 + max_groups * stride) * 8));
+  unsigned long long* d_keys = d_ws;
+  unsigned long long* d_acc = d_keys + cap;
+  unsigned long long* d_misc = d_acc + acc_words;
+  unsigned long long* d_out = d_misc + 3;
+  a.gkeys = d_keys;
+  a.gacc = d_acc;
+  a.ginserts = (uint32_t*)d_misc;
+  a.goverflow = (uint32_t*)d_misc + 1;
+  a.rows_passed = d_misc + 1;
+
+  uint32_t nblocks =
+    (uint32_t)((tab->rows + a.group_rows - 1) / a.group_rows);
+  if (nblocks > SCAN_MAXB) nblocks = SCAN_MAXB;
+  if (nblocks < 1) nblocks = 1;
+  const uint32_t cblocks =
+    (uint32_t)std::min<uint64_t>(1024, (cap + 255) / 256);
+
+  std::vector<unsigned long long> h_out;  // [n * stride], as d_out
+  unsigned long long h_misc[3] = {0, 0, 0};
+  uint64_t n = 0;
+  const uint32_t wit = naggs;                // first witness word
+  const uint32_t w_or = naggs + 2 * nkeys;   // OR of null masks; +1: of
+                                             // their complements
+  bool proved = false;
+  for (uint64_t seed = 0; seed < 4 && !proved; ++seed) {
+    a.seed = seed;
+    MK_CHECK(hipMemsetAsync(d_keys, 0xFF, cap * 8, stream));
+    MK_CHECK(hipMemsetAsync(d_acc, 0, (acc_words + 3) * 8, stream));
+    hipLaunchKernelGGL(scan_agg_hash_multi_kernel, dim3(nblocks),
+                       dim3(SCAN_NTHREADS), lds, stream, a);
+    MK_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(hash_multi_compact_kernel, dim3(cblocks), dim3(256),
+                       0, stream, d_keys, d_acc, (uint32_t)cap, stride,
+                       (uint32_t)max_groups, d_out, (uint32_t*)(d_misc + 2));
+    MK_CHECK(hipGetLastError());
+    MK_CHECK(hipMemcpyAsync(h_misc, d_misc, 24, hipMemcpyDeviceToHost,
+                            stream));
+    MK_CHECK(hipStreamSynchronize(stream));
+    const uint32_t inserts = (uint32_t)(h_misc[0] & 0xFFFFFFFFu);
+    const uint32_t overflow = (uint32_t)(h_misc[0] >> 32);
+    // distinct hashes never outnumber distinct tuples: too many is final
+    if (overflow || inserts > max_groups) {
+      release();
+      return SDB_ERR_OOM;
+    }
+    n = std::min<uint64_t>(h_misc[2] & 0xFFFFFFFFu, max_groups);
+    h_out.resize(n * stride);
+    if (n) {
+      MK_CHECK(hipMemcpyAsync(h_out.data(), d_out, n * stride * 8,
+                              hipMemcpyDeviceToHost, stream));
+      MK_CHECK(hipStreamSynchronize(stream));
+    }
+    // the witness: one null mask, and one value in each position it leaves
+    proved = true;
+    for (uint64_t i = 0; i < n && proved; ++i) {
+      const unsigned long long* w = &h_out[i * stride];
+      const unsigned long long nm = w[w_or];
+      proved = (nm & w[w_or + 1]) == 0;
+      for (uint32_t j = 0; j < nkeys && proved; ++j)
+        if (!((nm >> j) & 1ull))
+          proved = ~w[wit + 2 * j] == w[wit + 2 * j + 1];
+    }
+  }
+#undef MK_CHECK
+  release();
+  if (!proved) return SDB_ERR_COLLISION;
+
+  // tuples ascending, column by column as signed i64, NULL last in its
+  // column. Sorted as packed records (the slot's null mask, and per position
+  // the MAX code = key ^ sign, unsigned order = signed order), not through
+  // the slots.
+  struct Rec {
+    unsigned long long code[SDB_MAX_GROUP_KEYS];
+    uint32_t nullmask, slot;
+  };
+  std::vector<Rec> recs(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const unsigned long long* w = &h_out[(uint64_t)i * stride];
+    recs[i].nullmask = (uint32_t)w[w_or];
+    recs[i].slot = i;
+    for (uint32_t j = 0; j < SDB_MAX_GROUP_KEYS; ++j)
+      recs[i].code[j] = j < nkeys ? w[wit + 2 * j + 1] : 0;
+  }
+  std::sort(recs.begin(), recs.end(), [&](const Rec& x, const Rec& y) {
+    for (uint32_t j = 0; j < nkeys; ++j) {
+      const bool jx = (x.nullmask >> j) & 1u, jy = (y.nullmask >> j) & 1u;
+      if (jx != jy) return jy;
+      if (!jx && x.code[j] != y.code[j]) return x.code[j] < y.code[j];
+    }
+    return false;
+  });
+  for (size_t g = 0; g < n; ++g) {
+    const Rec& r = recs[g];
+    keynull_out[g] = r.nullmask;
+    for (uint32_t j = 0; j < nkeys; ++j)
+      keys_out[g * nkeys + j] =
+        ((r.nullmask >> j) & 1u) ? 0 : (int64_t)(r.code[j] ^ SDB_I64_SIGN);
+    for (uint32_t q = 0; q < naggs; ++q)
+      agg_decode(aggs[q].op, h_out[(uint64_t)r.slot * stride + q],
+                 &out[g * naggs + q]);
+  }
+  *ngroups_out = n;
+  *rows_passed = h_misc[1];
+  return SDB_OK;
 }
 
 // FNV-1a 64 over each row's DECODED string bytes (raw slot: the bytes
