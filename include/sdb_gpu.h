@@ -256,7 +256,17 @@ typedef struct SdbHybridPred {
 } SdbHybridPred;
 
 /* Single-predicate hybrid (BASELINE configs[3]): col0 BETWEEN [flo,fhi],
- * buckets over its value span. */
+ * buckets over its value span.
+ *
+ * Bucket rule (this entry, _chain and _batch): a survivor with value v
+ * lands in
+ *     bucket = floor((v - flo) * nbuckets / (fhi - flo + 1))
+ * in exact integer arithmetic, for any int64 flo <= fhi -- the full span
+ * flo = INT64_MIN, fhi = INT64_MAX (fhi - flo + 1 = 2^64) included; no
+ * intermediate wraps. 1 <= nbuckets <= 128. flo > fhi is an empty range:
+ * SDB_OK with total 0, no hits and every bucket zero. bucket_count[b] is
+ * the number of survivors in bucket b; bucket_sum[b] is the sum of their
+ * values as a wrap-around (mod 2^64) int64, as SDB_AGG_SUM_I64 is. */
 int sdb_gpu_execute_topk_hybrid(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
                                 uint32_t nsegs, const SdbQueryPlan* plan,
                                 uint32_t k, int64_t flo, int64_t fhi,
@@ -266,7 +276,9 @@ int sdb_gpu_execute_topk_hybrid(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
 
 /* Predicate-chain hybrid: preds[0] must be BETWEEN (it defines the bucket
  * span); preds[1..] are additional AND-ed predicates on any attached slot.
- * bucket_count/bucket_sum aggregate preds[0]'s column over full survivors. */
+ * bucket_count/bucket_sum aggregate preds[0]'s column over full survivors,
+ * by the bucket rule above with flo/fhi = preds[0].lo/hi (exact for any
+ * int64 lo <= hi; lo > hi is an empty result; sums wrap as int64). */
 int sdb_gpu_execute_topk_hybrid_chain(
   SdbGpuCtx* ctx, SdbGpuSegment* const* segs, uint32_t nsegs,
   const SdbQueryPlan* plan, uint32_t k, const SdbHybridPred* preds,

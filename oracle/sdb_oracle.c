@@ -645,12 +645,18 @@ static uint64_t o_exec_range(OCursor* cur, uint32_t nterms,
             --matches;
             continue;
           }
-          const uint64_t span = (uint64_t)(hy->hi - hy->lo) + 1;
-          uint32_t bkt =
-            (uint32_t)(((uint64_t)(v - hy->lo) * hy->nbuckets) / span);
-          if (bkt >= hy->nbuckets) bkt = hy->nbuckets - 1;
+          /* exact floor((v-lo)*nbuckets / (hi-lo+1)) for any int64
+           * lo <= v <= hi: unsigned subtraction (no signed overflow), the
+           * product and a span of up to 2^64 held in 128 bits */
+          const unsigned __int128 span =
+            (unsigned __int128)((uint64_t)hy->hi - (uint64_t)hy->lo) + 1;
+          const uint32_t bkt = (uint32_t)(
+            (unsigned __int128)((uint64_t)v - (uint64_t)hy->lo) *
+            hy->nbuckets / span);
           hy->bucket_count[bkt] += 1;
-          hy->bucket_sum[bkt] += v;
+          /* wrap-around int64 sum, as SDB_AGG_SUM_I64 */
+          hy->bucket_sum[bkt] =
+            (int64_t)((uint64_t)hy->bucket_sum[bkt] + (uint64_t)v);
         }
         const float s = score_win[w * 64 + bit];
         if (coll) {

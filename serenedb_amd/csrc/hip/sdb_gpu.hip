@@ -575,6 +575,9 @@ struct WindowArgs {
 // descriptors advance monotonically. Ablation history: the
 // per-window-grid version spent 0.18 ms in per-window init (dominated by
 // 2*nterms serial-latency binary searches) and ran 16 dispatch rounds.
+// WIDE: the hybrid bucket span needs sdb_bucket_wide (sdb_internal.h); the
+// host picks the instantiation per call
+template <bool WIDE>
 __launch_bounds__(SDB_NTHREADS, 1) __global__
 void topk_window_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -918,11 +921,13 @@ void topk_window_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
             cwin[off] = 0;
             continue;
           }
-          const unsigned long long span =
-            (unsigned long long)(a.fhi - a.flo) + 1ull;
-          uint32_t bkt = (uint32_t)(
-            ((unsigned long long)(vv - a.flo) * a.nbuckets) / span);
-          if (bkt >= a.nbuckets) bkt = a.nbuckets - 1;
+          const unsigned long long span_m1 =
+            (unsigned long long)a.fhi - (unsigned long long)a.flo;
+          const unsigned long long dv =
+            (unsigned long long)vv - (unsigned long long)a.flo;
+          const uint32_t bkt = WIDE
+            ? sdb_bucket_wide(dv, a.nbuckets, span_m1)
+            : sdb_bucket_narrow(dv, a.nbuckets, span_m1);
           atomicAdd(&lbuck[2 * bkt], 1ull);
           atomicAdd(&lbuck[2 * bkt + 1], (unsigned long long)vv);
         }
@@ -1109,7 +1114,8 @@ void topk_window_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
 //    windows at 2 workgroups/CU let one WG's decode cover the other's
 //    term barriers (the fixed 24576x1024 1-WG/CU shape left every barrier
 //    stall empty).
-template <uint32_t WD, uint32_t NTH>
+template <uint32_t WD, uint32_t NTH, bool WIDE>
+// WIDE as in topk_window_kernel.
 // 2nd launch-bounds arg = min waves/SIMD. A 1024-thread WG forces 4/SIMD
 // (VGPRs <= 128), and at that cap the kernel spills ~65 SGPRs to SCRATCH
 // (212 B/thread private segment measured via rocprofv3) — reloads in the
@@ -1600,11 +1606,13 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
             word &= ~(1ull << bit);
             continue;
           }
-          const unsigned long long span =
-            (unsigned long long)(a.fhi - a.flo) + 1ull;
-          uint32_t bkt = (uint32_t)(
-            ((unsigned long long)(vv - a.flo) * a.nbuckets) / span);
-          if (bkt >= a.nbuckets) bkt = a.nbuckets - 1;
+          const unsigned long long span_m1 =
+            (unsigned long long)a.fhi - (unsigned long long)a.flo;
+          const unsigned long long dv =
+            (unsigned long long)vv - (unsigned long long)a.flo;
+          const uint32_t bkt = WIDE
+            ? sdb_bucket_wide(dv, a.nbuckets, span_m1)
+            : sdb_bucket_narrow(dv, a.nbuckets, span_m1);
           atomicAdd(&lbuck[2 * bkt], 1ull);
           atomicAdd(&lbuck[2 * bkt + 1], (unsigned long long)vv);
         }
@@ -2324,10 +2332,19 @@ struct SweepGeom {
 // 16384x1024, 12288x512, 8192x512, 8192x256, 4096x256, 24576x512,
 // 32768x512 — selected at launch by SDB_SWEEP_GEOM
 
-bool launch_sweep(const SweepGeom& g, dim3 grid, size_t lds,
+bool launch_sweep(const SweepGeom& g, bool wide, dim3 grid, size_t lds,
                   hipStream_t st, const WindowArgs& a,
                   const TermDev* terms) {
-#define SDB_SWEEP_CASE(WDV, NTHV)                                         if (g.wd == WDV && g.nth == NTHV) {                                       hipLaunchKernelGGL((topk_sweep_kernel<WDV, NTHV>), grid, dim3(NTHV),                       lds, st, a, terms);                                  return true;                                                          }
+#define SDB_SWEEP_CASE(WDV, NTHV)                                          \
+  if (g.wd == WDV && g.nth == NTHV) {                                      \
+    if (wide)                                                              \
+      hipLaunchKernelGGL((topk_sweep_kernel<WDV, NTHV, true>), grid,       \
+                         dim3(NTHV), lds, st, a, terms);                   \
+    else                                                                   \
+      hipLaunchKernelGGL((topk_sweep_kernel<WDV, NTHV, false>), grid,      \
+                         dim3(NTHV), lds, st, a, terms);                   \
+    return true;                                                           \
+  }
   SDB_SWEEP_CASE(24576, 1024)
   SDB_SWEEP_CASE(16384, 1024)
   SDB_SWEEP_CASE(12288, 512)
@@ -2815,6 +2832,12 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
     }
   }
 
+  // hybrid bucket form, once per call (sdb_internal.h)
+  const bool wide_span =
+    hybrid && sdb_bucket_span_wide((unsigned long long)hpreds[0].hi -
+                                     (unsigned long long)hpreds[0].lo,
+                                   h_nbuckets);
+
   HIP_CHECK(hipEventRecord(ctx->ev_a, ctx->stream));
   for (uint32_t s = 0; s < nsegs; ++s) {
     SdbGpuSegment* seg = segs[s];
@@ -2909,7 +2932,7 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
       const uint32_t nwin = (seg->hdr.doc_count + sgeom.wd - 1) / sgeom.wd;
       uint32_t ngrid = 256u * s_wgs_per_cu;
       if (ngrid > nwin) ngrid = nwin;
-      if (!launch_sweep(sgeom, dim3(ngrid), s_lds, ctx->stream, a,
+      if (!launch_sweep(sgeom, wide_span, dim3(ngrid), s_lds, ctx->stream, a,
                         d_tslot))
         return SDB_ERR_INVALID;  // unknown SDB_SWEEP_GEOM instantiation
       HIP_CHECK(hipGetLastError());
@@ -2922,8 +2945,14 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
     if (wgs_per_cu > 4) wgs_per_cu = 4;
     uint32_t ngrid = 256u * wgs_per_cu;
     if (ngrid > nwin) ngrid = nwin;
-    hipLaunchKernelGGL(topk_window_kernel, dim3(ngrid), dim3(SDB_NTHREADS),
-                       lds_bytes, ctx->stream, a, d_tslot);
+    if (wide_span)
+      hipLaunchKernelGGL(topk_window_kernel<true>, dim3(ngrid),
+                         dim3(SDB_NTHREADS), lds_bytes, ctx->stream, a,
+                         d_tslot);
+    else
+      hipLaunchKernelGGL(topk_window_kernel<false>, dim3(ngrid),
+                         dim3(SDB_NTHREADS), lds_bytes, ctx->stream, a,
+                         d_tslot);
     HIP_CHECK(hipGetLastError());
   }
 
@@ -3089,6 +3118,12 @@ static int exec_topk_batch_impl(
   const float smax = ps.smax;
   const float inv_smax = (float)SDB_HIST_BINS / smax;
 
+  // hybrid bucket form, once per call (sdb_internal.h)
+  const bool wide_span =
+    hybrid && sdb_bucket_span_wide((unsigned long long)hpreds[0].hi -
+                                     (unsigned long long)hpreds[0].lo,
+                                   h_nbuckets);
+
   // path/geometry decisions identical to exec_topk_impl
   SweepGeom sgeom{24576, 1024};
   bool use_sweep = plan->min_match <= 1;
@@ -3245,7 +3280,7 @@ static int exec_topk_batch_impl(
           (seg->hdr.doc_count + sgeom.wd - 1) / sgeom.wd;
         uint32_t ngrid = 256u * s_wgs_per_cu;
         if (ngrid > nwin) ngrid = nwin;
-        if (!launch_sweep(sgeom, dim3(ngrid), s_lds, ctx->stream, a,
+        if (!launch_sweep(sgeom, wide_span, dim3(ngrid), s_lds, ctx->stream, a,
                           d_tslot))
           return SDB_ERR_INVALID;
         HIP_CHECK(hipGetLastError());
@@ -3262,12 +3297,16 @@ static int exec_topk_batch_impl(
       if (wgs_per_cu > 4) wgs_per_cu = 4;
       uint32_t ngrid = 256u * wgs_per_cu;
       if (ngrid > nwin) ngrid = nwin;
-      hipLaunchKernelGGL(topk_window_kernel, dim3(ngrid),
-                         dim3(SDB_NTHREADS),
-                         lds_fixed_gen +
-                           sizeof(SdbBlockDesc) * gen_dcache_n *
-                             plan->nterms,
-                         ctx->stream, a, d_tslot);
+      const size_t gen_lds =
+        lds_fixed_gen + sizeof(SdbBlockDesc) * gen_dcache_n * plan->nterms;
+      if (wide_span)
+        hipLaunchKernelGGL(topk_window_kernel<true>, dim3(ngrid),
+                           dim3(SDB_NTHREADS), gen_lds, ctx->stream, a,
+                           d_tslot);
+      else
+        hipLaunchKernelGGL(topk_window_kernel<false>, dim3(ngrid),
+                           dim3(SDB_NTHREADS), gen_lds, ctx->stream, a,
+                           d_tslot);
       HIP_CHECK(hipGetLastError());
     }
     // readback the tiny per-query state to its pinned mirror, then mark

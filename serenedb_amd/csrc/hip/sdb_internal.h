@@ -13,6 +13,55 @@ struct TermDev {
   float nl;   // norm_length = k*b/avgDL
 };
 
+// ---- hybrid bucket rule (sdb_gpu.h, "hybrid") ----
+// bucket = floor(d * nb / span), d = (u64)(v - lo), span = (hi - lo) + 1,
+// exact for every int64 lo <= v <= hi: span reaches 2^64 and d * nb 2^71.
+// The span travels as span_m1 = span - 1 = (u64)hi - (u64)lo, which always
+// fits; the subtraction is unsigned, so no signed overflow.
+//
+// The host decides once per call which of the two forms is exact and
+// launches the kernel instantiation compiled for it, so a narrow span runs
+// the one-multiply, one-divide code alone. A span is wide iff
+// span_m1 * nb >= 2^64, i.e. iff d * nb can leave 64 bits, or the span
+// itself is 2^64 (which nb = 1 reaches without the former).
+__host__ __device__ inline bool sdb_bucket_span_wide(
+  unsigned long long span_m1, uint32_t nb) {
+  return nb != 0 && (span_m1 == ~0ull || span_m1 > ~0ull / nb);
+}
+
+__host__ __device__ inline uint32_t sdb_bucket_narrow(
+  unsigned long long d, uint32_t nb, unsigned long long span_m1) {
+  uint32_t bkt = (uint32_t)((d * nb) / (span_m1 + 1ull));
+  if (bkt >= nb) bkt = nb - 1;
+  return bkt;
+}
+
+__host__ __device__ inline unsigned long long sdb_mul64hi(
+  unsigned long long x, unsigned long long y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul64hi(x, y);
+#else
+  return (unsigned long long)(((unsigned __int128)x * y) >> 64);
+#endif
+}
+
+// any span: the quotient is < nb <= 128 (as d < span), found in 7 steps of
+// a 128-bit compare; no 128-bit division on the device
+__host__ __device__ inline uint32_t sdb_bucket_wide(
+  unsigned long long d, uint32_t nb, unsigned long long span_m1) {
+  const unsigned long long nhi = sdb_mul64hi(d, nb), nlo = d * nb;
+  if (span_m1 == ~0ull) return (uint32_t)nhi;  // span = 2^64
+  const unsigned long long span = span_m1 + 1ull;
+  uint32_t q = 0;  // largest q < nb with q * span <= d * nb
+  for (uint32_t step = 64; step; step >>= 1) {
+    const uint32_t c = q + step;
+    if (c >= nb) continue;
+    const unsigned long long chi = sdb_mul64hi(c, span), clo = c * span;
+    if (chi < nhi || (chi == nhi && clo <= nlo)) q = c;
+  }
+  return q;
+}
+
 struct SdbGpuCtx {
   int device;
   hipStream_t stream;

@@ -527,8 +527,8 @@ def test_hybrid_vs_brute():
     bks = ((col[passing] - flo) * nbuckets // w).astype(np.int64)
     bks = np.minimum(bks, nbuckets - 1)
     exp_cnt = np.bincount(bks, minlength=nbuckets)
-    exp_sum = np.bincount(bks, weights=col[passing].astype(np.float64),
-                          minlength=nbuckets).astype(np.int64)
+    exp_sum = np.zeros(nbuckets, dtype=np.int64)   # exact: integer adds
+    np.add.at(exp_sum, bks, col[passing])
     np.testing.assert_array_equal(bcnt, exp_cnt)
     np.testing.assert_array_equal(bsum, exp_sum)
 
