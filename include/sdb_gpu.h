@@ -584,6 +584,83 @@ int sdb_gpu_scan_agg_hash_str(SdbGpuCtx* ctx, SdbGpuTable* tab,
                               uint64_t* ngroups_out,
                               uint64_t* rows_passed);
 
+/* ---- ORDER BY col [DESC] LIMIT k over the scan ----
+ * The row-returning half of the scan operator: SELECT ... WHERE preds ORDER
+ * BY order_col [DESC] LIMIT k, DuckDB's TopN over FullScanner::Scan ("the
+ * latest 100 events matching a filter"). order_col is I64, I64_FOR or F32.
+ * Predicates are exactly those of sdb_gpu_scan_agg_hash: up to 4, AND-ed;
+ * compares drop NULLs, ISNULL / NOTNULL read the plane, STRMASK consumes a
+ * slot mask.
+ *
+ * The result is the first min(k, rows passing) of the passing rows in the
+ * total order (NULL class, value, row ascending):
+ *   - i64 values order as signed integers; f32 values in the library's total
+ *     order, every NaN canonicalised:
+ *       -inf < ... < -0.0 < +0.0 < ... < +inf < NaN;
+ *   - SDB_TOPN_DESC reverses the value order only;
+ *   - ties are always by row ascending — a deterministic refinement of an
+ *     unspecified tie order, as (segment, doc) is for the BM25 top-k;
+ *   - a row whose order-column validity bit is cleared is NULL whatever it
+ *     stores. All passing NULL rows rank after every value (NULLS LAST, in
+ *     both directions, as DuckDB), or before every value under
+ *     SDB_TOPN_NULLS_FIRST, and among themselves by row ascending.
+ * rows_out[i] is the row number; vals_out[i] holds the value in the i64
+ * field for i64 / FoR columns and in the f64 field (the f32 widened, exact)
+ * for F32; a NaN returns as the canonical quiet NaN. NULL rows return zeros
+ * with null_out[i] = 1. *n_out = rows returned; *rows_passed counts every
+ * passing row. All three arrays hold k entries.
+ *
+ * k == 0, k > SDB_TOPN_MAX_K, order_col >= ncols, unknown flag bits and
+ * every bad predicate case of the entries above return SDB_ERR_INVALID
+ * before anything is launched, with the outputs untouched. An empty table or
+ * an empty pass set is SDB_OK with *n_out = 0.
+ *
+ * How it is exact: an MSD radix select over order-preserving u64 rank codes
+ * (11-bit digits, one histogram scan each) narrows the k-th code until the
+ * rows at or above its prefix fit the candidate buffer; a collect pass
+ * appends those (code, row) pairs and the host sorts them. When every digit
+ * is resolved and the rows equal to the k-th code still do not fit, or when
+ * NULL rows are needed, the row-order arm runs: members of that one class are
+ * counted per row group, and only the row groups up to the last one needed
+ * are collected, so the buffer never needs more than k + group_rows entries.
+ * A candidate overflow returns SDB_ERR_OOM; never a wrong answer.
+ *
+ * Device workspace (histogram, candidate buffer, per-row-group counts) is
+ * cached on the context and grown on demand: a repeated call allocates
+ * nothing.
+ *
+ * Test hook: the environment variable SDB_TOPN_CAND_CAP (read per call)
+ * replaces the default candidate capacity of 2^20 entries; the effective
+ * value is max(value, k + group_rows) and is reported in stats->cand_cap. It
+ * makes every arm reachable on a small table. Not for production use. */
+#define SDB_TOPN_MAX_K 65536u
+#define SDB_TOPN_DESC        1u   /* default ascending */
+#define SDB_TOPN_NULLS_FIRST 2u   /* default NULLS LAST, in both directions (DuckDB) */
+
+typedef struct SdbTopnStats {
+  uint32_t hist_passes;        /* histogram scans run */
+  uint32_t tie_arm;            /* 1 = the row-order arm ran */
+  uint64_t candidates;         /* entries the collect pass appended */
+  uint64_t cand_cap;           /* effective candidate capacity of this call */
+  uint32_t rowgroups_skipped;  /* row groups skipped by the ORDER column's zonemap, all passes */
+} SdbTopnStats;
+
+int sdb_gpu_scan_topn(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t order_col,
+                      uint32_t flags, uint32_t k, const SdbPredSpec* preds,
+                      uint32_t npreds, uint64_t* rows_out /* k */,
+                      SdbAggResult* vals_out /* k */,
+                      uint8_t* null_out /* k */, uint64_t* n_out,
+                      uint64_t* rows_passed,
+                      SdbTopnStats* stats /* may be NULL */);
+
+/* The rest of the SELECT list: value and NULL flag of column `col` (any
+ * type) at each of the n given rows, in the output convention above.
+ * n <= 2^20; a row >= the table's rows returns SDB_ERR_INVALID, checked on
+ * the host before anything is launched. */
+int sdb_gpu_table_gather(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t col,
+                         const uint64_t* rows, uint64_t n,
+                         SdbAggResult* out /* n */, uint8_t* null_out /* n */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -384,6 +384,7 @@ def gpu():
             "sdb_gpu_segment_attach_livemask",
             "sdb_gpu_execute_topk_batch", "sdb_gpu_table_attach_validity",
             "sdb_gpu_execute_match_docs", "sdb_gpu_execute_count",
+            "sdb_gpu_scan_topn", "sdb_gpu_table_gather",
         ):
             getattr(lib, f).restype = C.c_int
         _gpu = lib
@@ -402,6 +403,7 @@ class GpuContext:
                 f"sdb_gpu_ctx_create failed rc={rc} "
                 "(no MI355X visible? the GPU path has no CPU fallback)")
         self._segments = []
+        self._table_f32 = {}  # table handle -> per column: is it f32
 
     def close(self):
         if self._ctx:
@@ -764,9 +766,12 @@ class GpuContext:
                                           C.c_uint64(rows), C.byref(tab))
         if rc != 0:
             raise RuntimeError(f"sdb_gpu_table_load rc={rc}")
+        self._table_f32[tab.value] = tuple(
+            bool(a.dtype == np.float32) for a in arrays)
         return tab
 
     def free_table(self, tab):
+        self._table_f32.pop(tab.value, None)
         self._lib.sdb_gpu_table_free(self._ctx, tab)
 
     def attach_validity(self, tab, col, bits):
@@ -1089,6 +1094,86 @@ class GpuContext:
         keys = keys_out[:n]
         keynull = (null_out[:n, None] >> np.arange(nk, dtype=np.uint32)) & 1
         return keys, keynull.astype(bool), i64, f64, passed.value
+
+    # ---- ORDER BY col [DESC] LIMIT k, and the rest of the SELECT list ----
+
+    TOPN_MAX_K = 65536          # SDB_TOPN_MAX_K (include/sdb_gpu.h)
+    TOPN_DESC, TOPN_NULLS_FIRST = 1, 2
+
+    class _TopnStats(C.Structure):
+        _fields_ = [("hist_passes", C.c_uint32), ("tie_arm", C.c_uint32),
+                    ("candidates", C.c_uint64), ("cand_cap", C.c_uint64),
+                    ("rowgroups_skipped", C.c_uint32)]
+
+    def scan_topn(self, tab, order_col, k, preds, desc=False,
+                  nulls_first=False, stats=False, flags=None):
+        """SELECT ... WHERE preds ORDER BY order_col [DESC] LIMIT k
+        (sdb_gpu_scan_topn). preds as in scan_agg_hash. Returns (rows
+        uint64 [n], vals [n], isnull bool [n], rows_passed[, stats dict]):
+        the first min(k, rows passing) passing rows in the order (NULL class,
+        value, row ascending); NULLs last unless nulls_first, in both
+        directions; ties by row ascending. vals is int64 for an i64 / FoR
+        order column and float32 for an f32 one (NaN canonical), 0 where
+        isnull is set. flags overrides the two booleans with a raw flag
+        word. stats=True appends the SdbTopnStats fields as a dict."""
+        import numpy as np
+
+        if flags is None:
+            flags = (self.TOPN_DESC if desc else 0) | \
+                (self.TOPN_NULLS_FIRST if nulls_first else 0)
+        cap = max(int(k), 1) if 0 < int(k) <= self.TOPN_MAX_K else 1
+        rows = np.zeros(cap, dtype=np.uint64)
+        isnull = np.zeros(cap, dtype=np.uint8)
+        out = (self._AggResult * cap)()
+        n = C.c_uint64(0)
+        passed = C.c_uint64(0)
+        st = self._TopnStats()
+        rc = self._lib.sdb_gpu_scan_topn(
+            self._ctx, tab, C.c_uint32(order_col), C.c_uint32(flags),
+            C.c_uint32(k), self._pred_specs(preds), C.c_uint32(len(preds)),
+            rows.ctypes.data_as(C.POINTER(C.c_uint64)), out,
+            isnull.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(n),
+            C.byref(passed), C.byref(st))
+        if rc != 0:
+            raise RuntimeError(f"sdb_gpu_scan_topn rc={rc}")
+        n = n.value
+        i64, f64 = self._unpack_aggs(out, n, 1)
+        vals = self._topn_vals(tab, order_col, i64[:, 0], f64[:, 0])
+        res = (rows[:n].copy(), vals, isnull[:n].astype(bool), passed.value)
+        if stats:
+            res += ({f: getattr(st, f) for f, _ in st._fields_},)
+        return res
+
+    def _topn_vals(self, tab, col, i64, f64):
+        """one result column in the column's own type: the f64 field of an
+        f32 column holds a widened f32, so narrowing it back is exact"""
+        import numpy as np
+
+        is_f32 = self._table_f32.get(tab.value, ())
+        if col < len(is_f32) and is_f32[col]:
+            return f64.astype(np.float32)
+        return i64
+
+    def gather(self, tab, col, rows):
+        """Value and NULL flag of column `col` at each row of `rows`
+        (sdb_gpu_table_gather): (vals [n], isnull bool [n]), vals int64 for
+        an i64 / FoR column, float32 for an f32 one, 0 where NULL. A row
+        outside the table raises (rc=-1)."""
+        import numpy as np
+
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        n = len(r)
+        out = (self._AggResult * max(n, 1))()
+        isnull = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = self._lib.sdb_gpu_table_gather(
+            self._ctx, tab, C.c_uint32(col),
+            r.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_uint64(n), out,
+            isnull.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if rc != 0:
+            raise RuntimeError(f"sdb_gpu_table_gather rc={rc}")
+        i64, f64 = self._unpack_aggs(out, n, 1)
+        return (self._topn_vals(tab, col, i64[:, 0], f64[:, 0]),
+                isnull[:n].astype(bool))
 
 
     def execute_topk_batch(self, segs, term_idx, boosts, k, nq,

@@ -2494,6 +2494,9 @@ int sdb_gpu_ctx_destroy(SdbGpuCtx* ctx) {
   if (!ctx) return SDB_ERR_INVALID;
   (void)hipFree(ctx->d_scan_out);
   (void)hipFree(ctx->d_scan_passed);
+  (void)hipFree(ctx->d_topn_hist);
+  (void)hipFree(ctx->d_topn_cand);
+  (void)hipFree(ctx->d_topn_rg);
   (void)hipFree(ctx->d_cands2);
   (void)hipFree(ctx->d_ghist2);
   (void)hipFree(ctx->d_qmisc);

@@ -101,4 +101,11 @@ struct SdbGpuCtx {
   float last_gtau;
   double last_readback_ms;
   double last_select_ms;
+  // cached sdb_gpu_scan_topn workspace, grown on demand like d_scan_out:
+  // digit histogram + counters, candidate buffer, per-row-group counts
+  unsigned long long* d_topn_hist;
+  void* d_topn_cand;
+  uint64_t topn_cand_cap;  // entries
+  uint32_t* d_topn_rg;
+  uint64_t topn_rg_cap;    // row groups
 };

@@ -1467,6 +1467,356 @@ void scan_agg_hash_multi_kernel(HashAggArgsMK a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// ORDER BY col [DESC] LIMIT k over the scan (sdb_gpu_scan_topn): an exact MSD
+// radix select, then a collect pass. Every passing non-NULL row has a rank
+// code, a u64 where BIGGER RANKS FIRST: i64 DESC is x ^ 2^63 (the MAX_I64
+// code of agg_row), ASC its complement; f32 is the 32-bit f32_order_key,
+// complemented within 32 bits for ASC, so a code is W = 64 or 32 bits wide.
+// NULL is a class of its own and never a code (INT64_MIN DESC is code 0).
+//
+// One kernel body, three modes, in the unstaged walker's shape (a workgroup
+// per row group, grid-strided, predicate zonemap skips):
+//   HIST     histogram of the next 11-bit digit over the rows whose higher
+//            digits equal the prefix the host has chosen so far; 2048 u32 bins
+//            in LDS, flushed once per workgroup into the global u64 bins.
+//            The first pass also counts rows passed and passing NULL rows.
+//   COUNT    members of one class (code == thr, or NULL) per row group, for
+//            the row-order arm: each row group belongs to one workgroup, which
+//            stores its count with a plain store.
+//   COLLECT  appends (code, row): code > thr from every row group, code == thr
+//            (or NULL, for the NULL class) from row groups < tie_rg_end only.
+//            Appends are wave-aggregated (ballot, one cursor add per wave,
+//            lanes write at base + rank), first into an LDS stage that the
+//            workgroup moves to the candidate buffer with one add on the
+//            global cursor per row group, and straight to the global cursor
+//            once the stage is full. Every global store is bounds-checked
+//            against cand_cap.
+// A FoR order column skips row groups on its own zonemap in every value mode;
+// the NULL class never does (a NULL row's stored value is not its rank).
+// ---------------------------------------------------------------------------
+#define TOPN_BINS 2048u
+#define TOPN_MISC 8u  // words after the bins: rows passed, NULL rows passed,
+                      // collect cursor, overflow flag, row groups skipped
+#ifndef TOPN_STAGE
+#define TOPN_STAGE 4096u  // candidates a workgroup stages in LDS (64 KiB)
+#endif
+enum { TOPN_HIST = 0, TOPN_COUNT = 1, TOPN_COLLECT = 2 };
+
+struct TopnCand {
+  unsigned long long code, row;
+};
+
+struct TopnArgs {
+  ColRef order;
+  const unsigned long long* order_valid;  // null = no NULL rows
+  uint64_t rows;
+  uint32_t group_rows;
+  uint32_t desc;
+  uint32_t npreds;
+  ColRef pred_col[SCAN_MAX_PREDS];
+  int pred_op[SCAN_MAX_PREDS];
+  int pred_isf32[SCAN_MAX_PREDS];
+  int64_t pred_lo[SCAN_MAX_PREDS];
+  int64_t pred_hi[SCAN_MAX_PREDS];
+  float pred_flo[SCAN_MAX_PREDS], pred_fhi[SCAN_MAX_PREDS];
+  const unsigned long long* pred_valid[SCAN_MAX_PREDS];
+  // HIST: rows with (code & prefix_mask) == prefix, digit (code >> shift) &
+  // digit_mask; first = this pass also counts rows passed / NULL rows
+  unsigned long long prefix_mask, prefix;
+  uint32_t shift, digit_mask;
+  uint32_t first;
+  unsigned long long* hist;  // [TOPN_BINS]
+  unsigned long long* misc;  // [TOPN_MISC]
+  // COUNT / COLLECT
+  uint32_t cls_null;    // the class is NULL, not code == thr
+  uint32_t tie_rg_end;  // class members count from row groups below this
+  unsigned long long thr;
+  uint32_t* rg_count;   // [row groups]
+  TopnCand* cand;
+  unsigned long long cand_cap;
+};
+
+// OT: 0 = raw i64, 1 = FoR i64, 2 = f32
+template <int OT>
+__device__ __forceinline__ unsigned long long topn_code(const TopnArgs& a,
+                                                        uint32_t rg,
+                                                        uint64_t r0,
+                                                        uint64_t r) {
+  if (OT == 2) {
+    const uint32_t key = f32_order_key(((const float*)a.order.data)[r]);
+    return a.desc ? key : (uint32_t)~key;
+  }
+  const int64_t x = OT == 1 ? col_read(a.order, rg, r0, r)
+                            : ((const long long*)a.order.data)[r];
+  const unsigned long long c = (unsigned long long)x ^ SDB_I64_SIGN;
+  return a.desc ? c : ~c;
+}
+
+// the AND of the predicates on row r. ISNULL / NOTNULL read the plane alone
+// and no column: a STRMASK predicate arrives as NOTNULL over the slot's mask
+// with no column behind it.
+__device__ __forceinline__ bool topn_pass(const TopnArgs& a, uint32_t rg,
+                                          uint64_t r0, uint64_t r) {
+  bool ok = true;
+  for (uint32_t p = 0; p < a.npreds; ++p) {
+    const int op = a.pred_op[p];
+    const unsigned long long* vb = a.pred_valid[p];
+    if (op == SDB_PRED_ISNULL)
+      ok &= vb && !valid_at(vb, r);
+    else if (op == SDB_PRED_NOTNULL)
+      ok &= valid_at(vb, r);
+    else if (a.pred_isf32[p])
+      ok &= pred_eval_fv(op, vb, r, ((const float*)a.pred_col[p].data)[r],
+                         a.pred_flo[p], a.pred_fhi[p]);
+    else
+      ok &= pred_eval_iv(op, vb, r, col_read(a.pred_col[p], rg, r0, r),
+                         a.pred_lo[p], a.pred_hi[p]);
+  }
+  return ok;
+}
+
+template <int OT, int MODE>
+__launch_bounds__(SCAN_NTHREADS) __global__ void topn_kernel(TopnArgs a) {
+  __shared__ uint32_t lh[MODE == TOPN_HIST ? TOPN_BINS : 1];
+  // COLLECT: the candidates of one row group, staged so that a sparse row
+  // group costs one add on the global cursor, not one per emitting wave
+  __shared__ TopnCand lbuf[MODE == TOPN_COLLECT ? TOPN_STAGE : 1];
+  __shared__ uint32_t lcnt;
+  __shared__ unsigned long long lbase;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t n_rowgroups =
+    (uint32_t)((a.rows + a.group_rows - 1) / a.group_rows);
+  unsigned long long my_passed = 0, my_null = 0;
+  if (MODE == TOPN_HIST) {
+    for (uint32_t i = threadIdx.x; i < TOPN_BINS; i += SCAN_NTHREADS)
+      lh[i] = 0;
+    __syncthreads();
+  }
+
+  for (uint32_t rg = blockIdx.x; rg < n_rowgroups; rg += gridDim.x) {
+    const uint64_t r0 = (uint64_t)rg * a.group_rows;
+    const uint64_t r1 = min(a.rows, r0 + a.group_rows);
+    bool dead = false;  // predicate zonemaps, as in the aggregate walkers
+    for (uint32_t p = 0; p < a.npreds; ++p) {
+      if (a.pred_col[p].desc && !a.pred_isf32[p]) {
+        const SdbColGroupDescDev& d = a.pred_col[p].desc[rg];
+        switch (a.pred_op[p]) {
+          case SDB_PRED_LT: dead |= d.vmin >= a.pred_lo[p]; break;
+          case SDB_PRED_GE: dead |= d.vmax < a.pred_lo[p]; break;
+          case SDB_PRED_BETWEEN:
+            dead |= (d.vmax < a.pred_lo[p]) | (d.vmin > a.pred_hi[p]);
+            break;
+          case SDB_PRED_EQ:
+            dead |= (d.vmax < a.pred_lo[p]) | (d.vmin > a.pred_lo[p]);
+            break;
+          default: break;
+        }
+      }
+    }
+    if (MODE != TOPN_HIST && a.cls_null && rg >= a.tie_rg_end) dead = true;
+    // the ORDER column's own zonemap: the code range of the row group
+    // against what this pass can still use. Never for the NULL class.
+    if (OT == 1 && !dead && !(MODE != TOPN_HIST && a.cls_null)) {
+      const SdbColGroupDescDev& d = a.order.desc[rg];
+      const unsigned long long lo = (unsigned long long)d.vmin ^ SDB_I64_SIGN;
+      const unsigned long long hi = (unsigned long long)d.vmax ^ SDB_I64_SIGN;
+      const unsigned long long cmin = a.desc ? lo : ~hi;
+      const unsigned long long cmax = a.desc ? hi : ~lo;
+      bool odead;
+      if (MODE == TOPN_HIST)
+        odead = (cmax < a.prefix) | (cmin > (a.prefix | ~a.prefix_mask));
+      else if (MODE == TOPN_COUNT)
+        odead = (a.thr < cmin) | (a.thr > cmax);
+      else
+        odead = (cmax < a.thr) | (cmax == a.thr && rg >= a.tie_rg_end);
+      if (odead) {
+        if (threadIdx.x == 0) atomicAdd(&a.misc[4], 1ull);
+        dead = true;
+      }
+    }
+    if (dead) {
+      if (MODE == TOPN_COUNT && threadIdx.x == 0) a.rg_count[rg] = 0;
+      continue;
+    }
+    if (MODE == TOPN_COUNT) {
+      if (threadIdx.x == 0) lh[0] = 0;
+      __syncthreads();
+    }
+    if (MODE == TOPN_COLLECT) {
+      if (threadIdx.x == 0) lcnt = 0;
+      __syncthreads();
+    }
+
+    // every lane of the workgroup runs every trip (a row past r1 merely
+    // fails), so the ballots below see whole waves
+    for (uint64_t b = r0; b < r1; b += SCAN_NTHREADS) {
+      const uint64_t r = b + threadIdx.x;
+      const bool ok = r < r1 && topn_pass(a, rg, r0, r);
+      const bool isnull = ok && !valid_at(a.order_valid, r);
+      const bool val = ok && !isnull;
+      unsigned long long code = 0;
+      if (val && !(MODE != TOPN_HIST && a.cls_null))
+        code = topn_code<OT>(a, rg, r0, r);
+
+      if (MODE == TOPN_HIST) {
+        if (a.first) {
+          my_passed += ok;
+          my_null += isnull;
+        }
+        const bool in = val && (code & a.prefix_mask) == a.prefix;
+        const uint32_t dg = (uint32_t)(code >> a.shift) & a.digit_mask;
+        const unsigned long long m = __ballot(in);
+        if (m) {
+          // sorted and low-cardinality columns put a whole wave into one
+          // bin: one lane adds the popcount instead of 64 adds serialising
+          // on one LDS address
+          const int lead = __ffsll((long long)m) - 1;
+          const uint32_t d0 = (uint32_t)__shfl((int)dg, lead, 64);
+          if (__ballot(in && dg == d0) == m) {
+            if ((int)lane == lead) atomicAdd(&lh[d0], (uint32_t)__popcll(m));
+          } else if (in) {
+            atomicAdd(&lh[dg], 1u);
+          }
+        }
+      } else if (MODE == TOPN_COUNT) {
+        const bool member = a.cls_null ? isnull : (val && code == a.thr);
+        const unsigned long long m = __ballot(member);
+        if (m && lane == 0) atomicAdd(&lh[0], (uint32_t)__popcll(m));
+      } else {
+        const bool emit =
+          a.cls_null ? isnull
+                     : (val && (code > a.thr ||
+                                (code == a.thr && rg < a.tie_rg_end)));
+        const unsigned long long m = __ballot(emit);
+        if (m) {
+          // wave-aggregated append into the workgroup's LDS stage: one LDS
+          // cursor add per wave, lanes write at base + rank
+          const int lead = __ffsll((long long)m) - 1;
+          const uint32_t rank =
+            (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+          uint32_t lb = 0;
+          if ((int)lane == lead)
+            lb = atomicAdd(&lcnt, (uint32_t)__popcll(m));
+          lb = (uint32_t)__shfl((int)lb, lead, 64);
+          const bool staged = emit && lb + rank < TOPN_STAGE;
+          if (staged) lbuf[lb + rank] = TopnCand{code, r};
+          // stage full: the rest of the wave goes to the global cursor,
+          // again one add per wave
+          const unsigned long long ms = __ballot(emit && !staged);
+          if (ms) {
+            const int lead2 = __ffsll((long long)ms) - 1;
+            unsigned long long base = 0;
+            if ((int)lane == lead2)
+              base = atomicAdd(&a.misc[2], (unsigned long long)__popcll(ms));
+            base = __shfl(base, lead2, 64);
+            if (emit && !staged) {
+              const unsigned long long idx =
+                base +
+                (unsigned long long)__popcll(ms & ((1ull << lane) - 1ull));
+              if (idx < a.cand_cap)
+                a.cand[idx] = TopnCand{code, r};
+              else
+                atomicOr(&a.misc[3], 1ull);  // the host returns SDB_ERR_OOM
+            }
+          }
+        }
+      }
+    }
+    if (MODE == TOPN_COLLECT) {
+      // the row group's stage into the candidate buffer: one global cursor
+      // add per workgroup, every store bounds-checked
+      __syncthreads();
+      const uint32_t ns = min(lcnt, TOPN_STAGE);
+      if (threadIdx.x == 0 && ns)
+        lbase = atomicAdd(&a.misc[2], (unsigned long long)ns);
+      __syncthreads();
+      for (uint32_t i = threadIdx.x; i < ns; i += SCAN_NTHREADS) {
+        const unsigned long long idx = lbase + i;
+        if (idx < a.cand_cap)
+          a.cand[idx] = lbuf[i];
+        else
+          atomicOr(&a.misc[3], 1ull);
+      }
+    }
+    if (MODE == TOPN_COUNT) {
+      __syncthreads();
+      if (threadIdx.x == 0) a.rg_count[rg] = lh[0];
+    }
+  }
+
+  if (MODE == TOPN_HIST) {
+    if (a.first) {
+#pragma unroll
+      for (int off = 32; off; off >>= 1) {
+        my_passed += __shfl_down(my_passed, off, 64);
+        my_null += __shfl_down(my_null, off, 64);
+      }
+      if (lane == 0 && my_passed) atomicAdd(&a.misc[0], my_passed);
+      if (lane == 0 && my_null) atomicAdd(&a.misc[1], my_null);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < TOPN_BINS; i += SCAN_NTHREADS)
+      if (lh[i]) atomicAdd(&a.hist[i], (unsigned long long)lh[i]);
+  }
+}
+
+// value and NULL flag of one column at n given rows (sdb_gpu_table_gather).
+// type: SdbColType. i64 values travel as their bits, f32 as the float's bits
+// in the low word, every NaN canonicalised; a NULL row returns 0.
+struct GatherArgs {
+  ColRef col;
+  const unsigned long long* valid;
+  int type;
+  uint32_t group_rows;
+  const unsigned long long* rows;
+  uint64_t n;
+  unsigned long long* vals;
+  uint8_t* nulls;
+};
+
+__global__ void table_gather_kernel(GatherArgs g) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.n) return;
+  const uint64_t r = g.rows[i];
+  const bool isnull = !valid_at(g.valid, r);
+  unsigned long long v = 0;
+  if (!isnull) {
+    if (g.type == SDB_COL_F32) {
+      uint32_t b = __float_as_uint(((const float*)g.col.data)[r]);
+      if ((b & 0x7FFFFFFFu) > 0x7F800000u) b = 0x7FC00000u;
+      v = b;
+    } else {
+      const uint32_t rg = (uint32_t)(r / g.group_rows);
+      v = (unsigned long long)col_read(g.col, rg,
+                                       (uint64_t)rg * g.group_rows, r);
+    }
+  }
+  g.vals[i] = v;
+  g.nulls[i] = isnull ? 1 : 0;
+}
+
+template <int OT>
+static void topn_launch_ot(int mode, uint32_t nblocks, hipStream_t stream,
+                           const TopnArgs& a) {
+  if (mode == TOPN_HIST)
+    hipLaunchKernelGGL((topn_kernel<OT, TOPN_HIST>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), 0, stream, a);
+  else if (mode == TOPN_COUNT)
+    hipLaunchKernelGGL((topn_kernel<OT, TOPN_COUNT>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), 0, stream, a);
+  else
+    hipLaunchKernelGGL((topn_kernel<OT, TOPN_COLLECT>), dim3(nblocks),
+                       dim3(SCAN_NTHREADS), 0, stream, a);
+}
+
+static void topn_launch(int ot, int mode, uint32_t nblocks,
+                        hipStream_t stream, const TopnArgs& a) {
+  if (ot == 2) topn_launch_ot<2>(mode, nblocks, stream, a);
+  else if (ot == 1) topn_launch_ot<1>(mode, nblocks, stream, a);
+  else topn_launch_ot<0>(mode, nblocks, stream, a);
+}
+
 extern "C" {
 
 static void table_free_str(SdbGpuTable* tab) {
@@ -2783,6 +3133,326 @@ int sdb_gpu_scan_agg_hash_str(SdbGpuCtx* ctx, SdbGpuTable* tab,
                                     ngroups_out, rows_passed);
   (void)hipFree(d_hash);
   return rc;
+}
+
+// ---- ORDER BY col [DESC] LIMIT k (include/sdb_gpu.h; the scheme is
+// described at topn_kernel) ----
+
+int sdb_gpu_scan_topn(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t order_col,
+                      uint32_t flags, uint32_t k, const SdbPredSpec* preds,
+                      uint32_t npreds, uint64_t* rows_out,
+                      SdbAggResult* vals_out, uint8_t* null_out,
+                      uint64_t* n_out, uint64_t* rows_passed,
+                      SdbTopnStats* stats) {
+  if (!ctx || !tab || !rows_out || !vals_out || !null_out || !n_out ||
+      !rows_passed || k == 0 || k > SDB_TOPN_MAX_K ||
+      order_col >= tab->ncols ||
+      (flags & ~(SDB_TOPN_DESC | SDB_TOPN_NULLS_FIRST)) ||
+      npreds > SCAN_MAX_PREDS || (npreds && !preds))
+    return SDB_ERR_INVALID;
+  TopnArgs a{};
+  a.order = tab->refs[order_col];
+  a.order_valid = tab->valid[order_col];
+  a.rows = tab->rows;
+  a.group_rows = tab->group_rows;
+  a.desc = (flags & SDB_TOPN_DESC) ? 1u : 0u;
+  a.npreds = npreds;
+  for (uint32_t p = 0; p < npreds; ++p) {
+    if (preds[p].op == SDB_PRED_STRMASK) {
+      // the slot's precomputed row bitmask, read as a plane: NOTNULL
+      // evaluates it alone and topn_pass reads no column for it
+      const uint32_t slot = preds[p].col;
+      if (slot >= SDB_MAX_STRCOLS || !tab->str_mask_set[slot])
+        return SDB_ERR_INVALID;
+      a.pred_col[p] = ColRef{nullptr, nullptr};
+      a.pred_op[p] = SDB_PRED_NOTNULL;
+      a.pred_valid[p] = tab->str_mask[slot];
+      continue;
+    }
+    if (preds[p].col >= tab->ncols) return SDB_ERR_INVALID;
+    if (preds[p].op < SDB_PRED_LT || preds[p].op > SDB_PRED_NOTNULL)
+      return SDB_ERR_INVALID;
+    a.pred_col[p] = tab->refs[preds[p].col];
+    a.pred_op[p] = preds[p].op;
+    a.pred_isf32[p] = tab->types[preds[p].col] == SDB_COL_F32 ? 1 : 0;
+    a.pred_lo[p] = preds[p].ilo;
+    a.pred_hi[p] = preds[p].ihi;
+    a.pred_flo[p] = preds[p].flo;
+    a.pred_fhi[p] = preds[p].fhi;
+    a.pred_valid[p] = tab->valid[preds[p].col];
+  }
+  const bool isf32 = tab->types[order_col] == SDB_COL_F32;
+  const int ot = isf32 ? 2 : (a.order.desc ? 1 : 0);
+  const bool nulls_first = (flags & SDB_TOPN_NULLS_FIRST) != 0;
+
+  // candidate capacity: 2^20 entries, or the SDB_TOPN_CAND_CAP test hook,
+  // never below what the row-order arm needs
+  uint64_t cand_cap = 1ull << 20;
+  if (const char* e = std::getenv("SDB_TOPN_CAND_CAP"))
+    cand_cap = std::strtoull(e, nullptr, 10);
+  cand_cap = std::max<uint64_t>(cand_cap, (uint64_t)k + tab->group_rows);
+
+  SdbTopnStats st{};
+  st.cand_cap = cand_cap;
+  *n_out = 0;
+  *rows_passed = 0;
+  if (tab->rows == 0) {
+    if (stats) *stats = st;
+    return SDB_OK;
+  }
+
+#define TOPN_CHECK(x)                                        \
+  do {                                                       \
+    hipError_t _e = (x);                                     \
+    if (_e != hipSuccess) {                                  \
+      return _e == hipErrorNoDevice ? SDB_ERR_NO_GPU         \
+             : _e == hipErrorOutOfMemory ? SDB_ERR_OOM       \
+                                         : SDB_ERR_HIP;      \
+    }                                                        \
+  } while (0)
+  hipStream_t stream = ctx->stream;
+  const uint64_t n_rowgroups =
+    (tab->rows + tab->group_rows - 1) / tab->group_rows;
+  // ctx-cached workspace: a repeated call allocates nothing
+  if (!ctx->d_topn_hist)
+    TOPN_CHECK(hipMalloc(&ctx->d_topn_hist, 8ull * (TOPN_BINS + TOPN_MISC)));
+  if (ctx->topn_cand_cap < cand_cap) {
+    if (ctx->d_topn_cand) (void)hipFree(ctx->d_topn_cand);
+    ctx->d_topn_cand = nullptr;
+    ctx->topn_cand_cap = 0;
+    TOPN_CHECK(hipMalloc(&ctx->d_topn_cand, sizeof(TopnCand) * cand_cap));
+    ctx->topn_cand_cap = cand_cap;
+  }
+  if (ctx->topn_rg_cap < n_rowgroups) {
+    if (ctx->d_topn_rg) (void)hipFree(ctx->d_topn_rg);
+    ctx->d_topn_rg = nullptr;
+    ctx->topn_rg_cap = 0;
+    TOPN_CHECK(hipMalloc(&ctx->d_topn_rg, 4ull * n_rowgroups));
+    ctx->topn_rg_cap = n_rowgroups;
+  }
+  a.hist = ctx->d_topn_hist;
+  a.misc = ctx->d_topn_hist + TOPN_BINS;
+  a.rg_count = ctx->d_topn_rg;
+  a.cand = (TopnCand*)ctx->d_topn_cand;
+  a.cand_cap = cand_cap;
+  const uint32_t nblocks =
+    (uint32_t)std::min<uint64_t>(n_rowgroups, SCAN_MAXB);
+
+  std::vector<unsigned long long> h(TOPN_BINS + TOPN_MISC);
+  std::vector<uint32_t> h_rg;
+  std::vector<TopnCand> vcand, ncand;
+
+  // the first `want` members of a class in row order: count them per row
+  // group, find the last row group needed, collect up to it
+  auto count_class = [&](uint64_t want) -> int {
+    a.tie_rg_end = 0xFFFFFFFFu;
+    topn_launch(ot, TOPN_COUNT, nblocks, stream, a);
+    TOPN_CHECK(hipGetLastError());
+    h_rg.resize(n_rowgroups);
+    TOPN_CHECK(hipMemcpyAsync(h_rg.data(), a.rg_count, 4ull * n_rowgroups,
+                              hipMemcpyDeviceToHost, stream));
+    TOPN_CHECK(hipStreamSynchronize(stream));
+    uint64_t run = 0;
+    uint32_t g = 0;
+    for (; g < n_rowgroups; ++g) {
+      run += h_rg[g];
+      if (run >= want) break;
+    }
+    if (g == n_rowgroups) return SDB_ERR_HIP;  // the passes disagree
+    a.tie_rg_end = g + 1;
+    return SDB_OK;
+  };
+  auto collect = [&](std::vector<TopnCand>& dst) -> int {
+    TOPN_CHECK(hipMemsetAsync(a.misc + 2, 0, 16, stream));
+    topn_launch(ot, TOPN_COLLECT, nblocks, stream, a);
+    TOPN_CHECK(hipGetLastError());
+    TOPN_CHECK(hipMemcpyAsync(h.data() + TOPN_BINS, a.misc, 8ull * TOPN_MISC,
+                              hipMemcpyDeviceToHost, stream));
+    TOPN_CHECK(hipStreamSynchronize(stream));
+    const uint64_t n = h[TOPN_BINS + 2];
+    if (h[TOPN_BINS + 3] || n > cand_cap) return SDB_ERR_OOM;
+    st.candidates += n;
+    dst.resize(n);
+    if (n) TOPN_CHECK(hipMemcpy(dst.data(), a.cand, sizeof(TopnCand) * n,
+                                hipMemcpyDeviceToHost));
+    return SDB_OK;
+  };
+
+  // ---- histogram passes: digits of 11 bits from the top of the code ----
+  const uint32_t W = isf32 ? 32u : 64u;
+  const uint32_t ndigits = (W + 10u) / 11u;
+  uint64_t passed = 0, null_passed = 0, kv = 0, r_null = 0;
+  uint64_t above = 0, ge = 0;  // rows above the prefix's range / at or above
+  unsigned long long prefix = 0, prefix_mask = 0;
+  bool resolved = false;       // ge <= cand_cap: collect at the lower bound
+  for (uint32_t d = 0; d < ndigits; ++d) {
+    const uint32_t bits = std::min(11u, W - 11u * d);
+    const uint32_t shift = W - 11u * d - bits;
+    a.prefix = prefix;
+    a.prefix_mask = prefix_mask;
+    a.shift = shift;
+    a.digit_mask = (1u << bits) - 1u;
+    a.first = d == 0;
+    TOPN_CHECK(hipMemsetAsync(
+      a.hist, 0, 8ull * (TOPN_BINS + (d == 0 ? TOPN_MISC : 0u)), stream));
+    topn_launch(ot, TOPN_HIST, nblocks, stream, a);
+    TOPN_CHECK(hipGetLastError());
+    TOPN_CHECK(hipMemcpyAsync(h.data(), a.hist,
+                              8ull * (TOPN_BINS + TOPN_MISC),
+                              hipMemcpyDeviceToHost, stream));
+    TOPN_CHECK(hipStreamSynchronize(stream));
+    ++st.hist_passes;
+    if (d == 0) {
+      passed = h[TOPN_BINS + 0];
+      null_passed = h[TOPN_BINS + 1];
+      const uint64_t nonnull = passed - null_passed;
+      if (nulls_first) {
+        r_null = std::min<uint64_t>(k, null_passed);
+        kv = std::min<uint64_t>(k - r_null, nonnull);
+      } else {
+        kv = std::min<uint64_t>(k, nonnull);
+        r_null = std::min<uint64_t>(k - kv, null_passed);
+      }
+      if (kv == 0) break;
+    }
+    // from the top bin down to the one in which the running count reaches kv
+    uint64_t run = above;
+    int b = (int)a.digit_mask;
+    for (; b >= 0; --b) {
+      if (run + h[b] >= kv) break;
+      run += h[b];
+    }
+    if (b < 0) return SDB_ERR_HIP;  // the passes disagree
+    above = run;
+    ge = run + h[b];
+    prefix |= (unsigned long long)b << shift;
+    prefix_mask |= (unsigned long long)a.digit_mask << shift;
+    if (ge <= cand_cap) {
+      resolved = true;
+      break;
+    }
+  }
+
+  // ---- values: everything at or above the prefix's lower bound, or, with
+  // every digit resolved and the ties at the k-th code still too many, the
+  // rows above it and the first kv - above of the ties in row order ----
+  if (kv) {
+    a.cls_null = 0;
+    a.thr = prefix;
+    a.tie_rg_end = 0xFFFFFFFFu;
+    if (!resolved) {
+      st.tie_arm = 1;
+      const int rc = count_class(kv - above);
+      if (rc) return rc;
+    }
+    const int rc = collect(vcand);
+    if (rc) return rc;
+    if (vcand.size() < kv) return SDB_ERR_HIP;
+    std::partial_sort(vcand.begin(), vcand.begin() + kv, vcand.end(),
+                      [](const TopnCand& x, const TopnCand& y) {
+                        return x.code != y.code ? x.code > y.code
+                                                : x.row < y.row;
+                      });
+  }
+  // ---- the NULL class: its first r_null members in row order ----
+  if (r_null) {
+    st.tie_arm = 1;
+    a.cls_null = 1;
+    a.thr = 0;
+    int rc = count_class(r_null);
+    if (rc) return rc;
+    rc = collect(ncand);
+    if (rc) return rc;
+    if (ncand.size() < r_null) return SDB_ERR_HIP;
+    std::partial_sort(ncand.begin(), ncand.begin() + r_null, ncand.end(),
+                      [](const TopnCand& x, const TopnCand& y) {
+                        return x.row < y.row;
+                      });
+  }
+#undef TOPN_CHECK
+  st.rowgroups_skipped = (uint32_t)h[TOPN_BINS + 4];
+
+  uint64_t n = 0;
+  auto emit_nulls = [&] {
+    for (uint64_t i = 0; i < r_null; ++i, ++n) {
+      rows_out[n] = ncand[i].row;
+      vals_out[n] = SdbAggResult{0, 0.0};
+      null_out[n] = 1;
+    }
+  };
+  if (nulls_first) emit_nulls();
+  for (uint64_t i = 0; i < kv; ++i, ++n) {
+    const unsigned long long c = vcand[i].code;
+    rows_out[n] = vcand[i].row;
+    null_out[n] = 0;
+    if (isf32) {
+      const uint32_t key = a.desc ? (uint32_t)c : ~(uint32_t)c;
+      const uint32_t fb =
+        (key & 0x80000000u) ? key ^ 0x80000000u : ~key;
+      float f;
+      std::memcpy(&f, &fb, 4);
+      vals_out[n] = SdbAggResult{0, (double)f};
+    } else {
+      vals_out[n] =
+        SdbAggResult{(int64_t)((a.desc ? c : ~c) ^ SDB_I64_SIGN), 0.0};
+    }
+  }
+  if (!nulls_first) emit_nulls();
+  *n_out = n;
+  *rows_passed = passed;
+  if (stats) *stats = st;
+  return SDB_OK;
+}
+
+int sdb_gpu_table_gather(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t col,
+                         const uint64_t* rows, uint64_t n, SdbAggResult* out,
+                         uint8_t* null_out) {
+  if (!ctx || !tab || col >= tab->ncols || n > (1ull << 20) ||
+      (n && (!rows || !out || !null_out)))
+    return SDB_ERR_INVALID;
+  for (uint64_t i = 0; i < n; ++i)
+    if (rows[i] >= tab->rows) return SDB_ERR_INVALID;
+  if (n == 0) return SDB_OK;
+  // one allocation: rows in, values out, NULL flags out
+  unsigned char* d_buf = nullptr;
+  HIP_CHECK(hipMalloc(&d_buf, 17ull * n));
+  GatherArgs g{};
+  g.col = tab->refs[col];
+  g.valid = tab->valid[col];
+  g.type = (int)tab->types[col];
+  g.group_rows = tab->group_rows;
+  g.rows = (const unsigned long long*)d_buf;
+  g.n = n;
+  g.vals = (unsigned long long*)(d_buf + 8ull * n);
+  g.nulls = d_buf + 16ull * n;
+  std::vector<unsigned long long> h_vals(n);
+  hipError_t e = hipMemcpyAsync(d_buf, rows, 8ull * n, hipMemcpyHostToDevice,
+                                ctx->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(table_gather_kernel, dim3((uint32_t)((n + 255) / 256)),
+                       dim3(256), 0, ctx->stream, g);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(h_vals.data(), g.vals, 8ull * n, hipMemcpyDeviceToHost,
+                       ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(null_out, g.nulls, n, hipMemcpyDeviceToHost,
+                       ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d_buf);
+  if (e != hipSuccess) return SDB_ERR_HIP;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (tab->types[col] == SDB_COL_F32) {
+      const uint32_t fb = (uint32_t)h_vals[i];
+      float f;
+      std::memcpy(&f, &fb, 4);
+      out[i] = SdbAggResult{0, null_out[i] ? 0.0 : (double)f};
+    } else {
+      out[i] = SdbAggResult{(int64_t)h_vals[i], 0.0};
+    }
+  }
+  return SDB_OK;
 }
 
 
