@@ -364,6 +364,21 @@ int sdb_gpu_table_attach_strcol_fsst(SdbGpuCtx* ctx, SdbGpuTable* tab,
                                      const uint32_t* sym_offsets,
                                      uint32_t nsym);
 
+/* One predicate of a scan. The column's type decides which literal pair a
+ * compare (LT, GE, BETWEEN, EQ) reads: an I64 or I64_FOR column reads
+ * ilo / ihi, an F32 column reads flo / fhi; the other pair is ignored.
+ * ihi / fhi matter to BETWEEN only.
+ *
+ * The f32 compares are IEEE-754 compares carried out in f32:
+ *   - a NaN in the column or in a literal fails LT, GE, BETWEEN and EQ
+ *     (so BETWEEN with a NaN bound, and EQ NaN, are empty);
+ *   - -0.0 equals +0.0, as a value and as a literal;
+ *   - subnormals are not flushed: they are distinct from zero and from
+ *     each other, in the column and in the literals;
+ *   - +-inf compare as the extremes; BETWEEN with lo > hi is empty.
+ * This is the order of a compare, not the total order MIN_F32 / MAX_F32 and
+ * the top-n use (where NaN is greatest and -0.0 < +0.0).
+ * tests/f32_matrix.py pins each of these on every scan path. */
 typedef struct SdbPredSpec {
   uint32_t col;
   SdbPredOp op;
@@ -388,6 +403,11 @@ typedef struct SdbPredSpec {
  * non-NULL passing value is NaN — the "NaN is the greatest value" rule of
  * the DuckDB consumer being replaced; -0.0 < +0.0 is a deterministic
  * refinement of it.
+ *
+ * SUM_F64 widens each f32 value to f64 (exact, subnormals included) and
+ * adds in f64 in an unspecified order. Over +-inf / NaN inputs the result
+ * is the IEEE sum: NaN if a NaN is summed or both infinities are, else the
+ * infinity that is summed; the NaN's sign and payload are unspecified.
  *
  * A group with no non-NULL passing value (an empty group of the dense
  * scan, or one whose passing rows are all NULL in `col`) returns the op's

@@ -868,9 +868,10 @@ class GpuContext:
 
     def scan_agg(self, tab, group_col, ngroups, preds, aggs):
         """preds: list of (col, op, lo, hi) with SdbPredOp numeric op
-        (1=LT 2=GE 3=BETWEEN 4=EQ); lo/hi int or float (float for f32
-        predicate columns). aggs: list of (col, op), op a name of AGG_OPS
-        or its number: 0=COUNT 1=SUM_I64 2=SUM_F64 3=COUNT_COL 4=MIN_I64
+        (1=LT 2=GE 3=BETWEEN 4=EQ 5=ISNULL 6=NOTNULL); the column's type
+        decides how lo/hi travel (_pred_specs): any real number on an f32
+        column, integers only on an i64 / FoR one (ValueError otherwise).
+        aggs: list of (col, op), op a name of AGG_OPS or its number: 0=COUNT 1=SUM_I64 2=SUM_F64 3=COUNT_COL 4=MIN_I64
         5=MAX_I64 6=MIN_F32 7=MAX_F32. Returns (i64 results [ngroups,
         naggs], f64 results [ngroups, naggs], rows_passed): COUNT, SUM_I64,
         COUNT_COL, MIN_I64 and MAX_I64 land in the i64 array, SUM_F64,
@@ -882,12 +883,7 @@ class GpuContext:
         import numpy as np
 
         np_ = len(preds)
-        pa = (self._PredSpec * max(np_, 1))()
-        for i, (col, op, lo, hi) in enumerate(preds):
-            if isinstance(lo, float) or isinstance(hi, float):
-                pa[i] = self._PredSpec(col, op, 0, 0, lo, hi)
-            else:
-                pa[i] = self._PredSpec(col, op, lo, hi, 0, 0)
+        pa = self._pred_specs(preds, tab)
         na = len(aggs)
         aa = self._agg_specs(aggs)
         out = (self._AggResult * (ngroups * na))()
@@ -913,12 +909,7 @@ class GpuContext:
         from oracle.pyoracle import fnv1a64
 
         np_ = len(preds)
-        pa = (self._PredSpec * max(np_, 1))()
-        for i, (col, op, lo, hi) in enumerate(preds):
-            if isinstance(lo, float) or isinstance(hi, float):
-                pa[i] = self._PredSpec(col, op, 0, 0, lo, hi)
-            else:
-                pa[i] = self._PredSpec(col, op, lo, hi, 0, 0)
+        pa = self._pred_specs(preds, tab)
         na = len(aggs)
         aa = self._agg_specs(aggs)
         keys = np.zeros(max_groups, dtype=np.int64)
@@ -966,12 +957,7 @@ class GpuContext:
         import numpy as np
 
         np_ = len(preds)
-        pa = (self._PredSpec * max(np_, 1))()
-        for i, (col, op, lo, hi) in enumerate(preds):
-            if isinstance(lo, float) or isinstance(hi, float):
-                pa[i] = self._PredSpec(col, op, 0, 0, lo, hi)
-            else:
-                pa[i] = self._PredSpec(col, op, lo, hi, 0, 0)
+        pa = self._pred_specs(preds, tab)
         na = len(aggs)
         aa = self._agg_specs(aggs)
         keys_out = np.zeros(max_groups, dtype=np.int64)
@@ -991,14 +977,48 @@ class GpuContext:
 
     # ---- GROUP BY a nullable key (a validity plane on the group column) ----
 
-    def _pred_specs(self, preds):
-        """[(col, op, lo, hi)] -> SdbPredSpec array (at least one slot)"""
+    def _pred_specs(self, preds, tab=None):
+        """[(col, op, lo, hi)] -> SdbPredSpec array (at least one slot).
+        The column's type picks the literal field of a compare (LT, GE,
+        BETWEEN, EQ), never the literal's Python type: on an f32 column any
+        real literal is rounded to float32 into flo / fhi; on an i64 / FoR
+        column the literal must be an integer (int or numpy integer), and a
+        float-typed one raises ValueError — the scan would read ilo / ihi,
+        so it would silently compare against something else. hi is a
+        literal for BETWEEN only. The other ops carry no literal. Every
+        entry of this class passes its table; without one (a hand-made call
+        of the C entry) no type is known and a float-typed literal is
+        taken to mean an f32 column."""
+        import numpy as np
+
+        def as_i64(col, lit):
+            if not isinstance(lit, (int, np.integer)):
+                raise ValueError(
+                    f"predicate on i64 column {col}: literal {lit!r} is not "
+                    "an integer")
+            return int(lit)
+
+        def col_is_f32(col, lo, hi):
+            if tab is None:
+                return isinstance(lo, (float, np.floating)) or isinstance(
+                    hi, (float, np.floating))
+            is_f32 = self._table_f32.get(tab.value, ())
+            return col < len(is_f32) and is_f32[col]
+
         pa = (self._PredSpec * max(len(preds), 1))()
         for i, (col, op, lo, hi) in enumerate(preds):
-            if isinstance(lo, float) or isinstance(hi, float):
-                pa[i] = self._PredSpec(col, op, 0, 0, lo, hi)
+            if op not in (1, 2, 3, 4):
+                pa[i] = self._PredSpec(col, op, 0, 0, 0, 0)
+            elif col_is_f32(col, lo, hi):
+                pa[i] = self._PredSpec(
+                    col, op, 0, 0, float(np.float32(lo)),
+                    float(np.float32(hi)) if op == 3 or isinstance(
+                        hi, (int, float, np.number)) else 0.0)
             else:
-                pa[i] = self._PredSpec(col, op, lo, hi, 0, 0)
+                pa[i] = self._PredSpec(
+                    col, op, as_i64(col, lo),
+                    as_i64(col, hi) if op == 3 or isinstance(
+                        hi, (int, np.integer)) else 0, 0, 0)
         return pa
 
     def scan_agg_nullkey(self, tab, group_col, ngroups, preds, aggs):
@@ -1010,13 +1030,14 @@ class GpuContext:
         identities when null_rows == 0), rows_passed includes the NULL-key
         rows. Valid keys must lie in [0, ngroups). Without a plane the
         first ngroups rows are scan_agg's."""
+        pa = self._pred_specs(preds, tab)
         na = len(aggs)
         out = (self._AggResult * ((ngroups + 1) * na))()
         passed = C.c_uint64(0)
         nulls = C.c_uint64(0)
         rc = self._lib.sdb_gpu_scan_agg_nullkey(
             self._ctx, tab, C.c_uint32(group_col), C.c_uint32(ngroups),
-            self._pred_specs(preds), C.c_uint32(len(preds)),
+            pa, C.c_uint32(len(preds)),
             self._agg_specs(aggs), C.c_uint32(na), out, C.byref(passed),
             C.byref(nulls))
         if rc != 0:
@@ -1035,6 +1056,7 @@ class GpuContext:
         it is apart from key -1 and takes no share of max_groups."""
         import numpy as np
 
+        pa = self._pred_specs(preds, tab)
         na = len(aggs)
         keys_out = np.zeros(max_groups, dtype=np.int64)
         out = (self._AggResult * (max_groups * na))()
@@ -1044,7 +1066,7 @@ class GpuContext:
         nulls = C.c_uint64(0)
         rc = self._lib.sdb_gpu_scan_agg_hash_nullkey(
             self._ctx, tab, C.c_uint32(group_col), C.c_uint64(max_groups),
-            self._pred_specs(preds), C.c_uint32(len(preds)),
+            pa, C.c_uint32(len(preds)),
             self._agg_specs(aggs), C.c_uint32(na),
             keys_out.ctypes.data_as(C.POINTER(C.c_int64)), out,
             C.byref(ng), C.byref(passed), null_out, C.byref(nulls))
@@ -1072,6 +1094,7 @@ class GpuContext:
         seeds in a row fail that proof)."""
         import numpy as np
 
+        pa = self._pred_specs(preds, tab)
         nk = len(group_cols)
         na = len(aggs)
         gc = (C.c_uint32 * max(nk, 1))(*group_cols)
@@ -1082,7 +1105,7 @@ class GpuContext:
         passed = C.c_uint64(0)
         rc = self._lib.sdb_gpu_scan_agg_hash_multi(
             self._ctx, tab, gc, C.c_uint32(nk), C.c_uint64(max_groups),
-            self._pred_specs(preds), C.c_uint32(len(preds)),
+            pa, C.c_uint32(len(preds)),
             self._agg_specs(aggs), C.c_uint32(na),
             keys_out.ctypes.data_as(C.POINTER(C.c_int64)),
             null_out.ctypes.data_as(C.POINTER(C.c_uint32)), out,
@@ -1121,6 +1144,7 @@ class GpuContext:
         if flags is None:
             flags = (self.TOPN_DESC if desc else 0) | \
                 (self.TOPN_NULLS_FIRST if nulls_first else 0)
+        pa = self._pred_specs(preds, tab)
         cap = max(int(k), 1) if 0 < int(k) <= self.TOPN_MAX_K else 1
         rows = np.zeros(cap, dtype=np.uint64)
         isnull = np.zeros(cap, dtype=np.uint8)
@@ -1130,7 +1154,7 @@ class GpuContext:
         st = self._TopnStats()
         rc = self._lib.sdb_gpu_scan_topn(
             self._ctx, tab, C.c_uint32(order_col), C.c_uint32(flags),
-            C.c_uint32(k), self._pred_specs(preds), C.c_uint32(len(preds)),
+            C.c_uint32(k), pa, C.c_uint32(len(preds)),
             rows.ctypes.data_as(C.POINTER(C.c_uint64)), out,
             isnull.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(n),
             C.byref(passed), C.byref(st))
