@@ -229,6 +229,10 @@ typedef enum SdbPredOp {
    * of sdb_gpu_strpred_mask (starts-with). */
   SDB_PRED_STRMASK = 7,
   SDB_PRED_PREFIX = 8,
+  /* ends-with lo / holds lo as a substring: like PREFIX, valid only as the
+   * `op` of sdb_gpu_strpred_mask / _ex (see there) */
+  SDB_PRED_SUFFIX = 9,
+  SDB_PRED_CONTAINS = 10,
 } SdbPredOp;
 
 int sdb_gpu_segment_attach_column(SdbGpuCtx* ctx, SdbGpuSegment* seg,
@@ -343,6 +347,80 @@ int sdb_gpu_table_attach_strcol(SdbGpuCtx* ctx, SdbGpuTable* tab,
 int sdb_gpu_strpred_mask(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t slot,
                          SdbPredOp op, const uint8_t* lo, uint32_t lo_len,
                          const uint8_t* hi, uint32_t hi_len);
+
+/* ---- SUFFIX, CONTAINS, LIKE, negation and mask combination ----
+ *
+ * Everything is byte-wise, like the rest of the string slots: NUL is an
+ * ordinary byte and matching is case sensitive.
+ *
+ * SDB_PRED_SUFFIX (row ends with lo) and SDB_PRED_CONTAINS (lo occurs in the
+ * row) take their literal in lo, 0..63 bytes; hi is ignored. The empty
+ * literal matches every well-formed row. sdb_gpu_strpred_mask accepts them
+ * too.
+ *
+ * sdb_gpu_strpred_mask_ex is sdb_gpu_strpred_mask plus `flags`
+ * (sdb_gpu_strpred_mask(...) == sdb_gpu_strpred_mask_ex(..., 0)):
+ *
+ *   SDB_STRPRED_NEGATE  the row result is inverted, for well-formed rows
+ *                       only: a malformed FSST row (below) still matches
+ *                       nothing, negated or not. String slots hold no NULLs,
+ *                       so over well-formed rows NEGATE is plain complement.
+ *   SDB_STRPRED_AND     the (possibly negated) result is AND-ed / OR-ed into
+ *   SDB_STRPRED_OR      the slot's current mask instead of replacing it, so
+ *                       `s >= 'a' AND s NOT LIKE '%bot%'` needs one slot.
+ *                       Both bits together are SDB_ERR_INVALID, and so is
+ *                       either on a slot whose mask was never computed since
+ *                       its attach.
+ *
+ * Any other bit is SDB_ERR_INVALID. Bits of the last mask word at rows >=
+ * rows stay 0 in every mode. A rejected call launches nothing and leaves
+ * the slot's mask as it was.
+ *
+ * sdb_gpu_strpred_like evaluates a LIKE pattern of up to
+ * SDB_LIKE_PATTERN_MAX bytes. A row matches iff the WHOLE row matches the
+ * pattern:
+ *   - '%' matches any byte sequence, the empty one included; consecutive
+ *     '%' collapse;
+ *   - the escape byte (escape = 0..255, or -1 for none) makes the byte after
+ *     it literal, whatever that byte is;
+ *   - every other byte is literal.
+ * So '' matches only the empty row and '%' every well-formed row. These are
+ * SDB_ERR_INVALID:
+ *   - an escape as the last pattern byte;
+ *   - an unescaped '_'. SQL's '_' stands for one CHARACTER and this library
+ *     compares BYTES: a byte-wise '_' would be silently wrong on UTF-8 data
+ *     (one code point is 1..4 bytes), so it is rejected rather than
+ *     approximated. Escape it to match the byte 0x5f;
+ *   - pattern_len > SDB_LIKE_PATTERN_MAX;
+ *   - more than SDB_STRLIT_MAX (63) literal bytes in total, counted after
+ *     the escapes are removed;
+ *   - escape outside -1..255, or escape == '%'.
+ * flags are those of sdb_gpu_strpred_mask_ex.
+ *
+ * Matching is leftmost-greedy over the pattern's literal segments (the runs
+ * between '%'), which decides LIKE exactly; serenedb_amd/csrc/sdb_like.h is
+ * the one matcher, compiled into the kernels and into libsdb_host.so
+ * (sdb_host_like_prog_size / sdb_host_like_compile / sdb_host_like_match).
+ *
+ * Test hook: the environment variable SDB_LIKE_ROWWISE=1 (read per call)
+ * makes a raw slot use the row-wise kernel where the cooperative
+ * substring kernel would run (one unanchored segment: CONTAINS, LIKE
+ * '%x%'). The masks are identical. Not for production use. */
+#define SDB_STRLIT_MAX 63
+#define SDB_LIKE_PATTERN_MAX 255
+#define SDB_STRPRED_NEGATE 1u
+#define SDB_STRPRED_AND 2u
+#define SDB_STRPRED_OR 4u
+
+int sdb_gpu_strpred_mask_ex(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t slot,
+                            SdbPredOp op, const uint8_t* lo, uint32_t lo_len,
+                            const uint8_t* hi, uint32_t hi_len,
+                            uint32_t flags);
+
+int sdb_gpu_strpred_like(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t slot,
+                         const uint8_t* pattern, uint32_t pattern_len,
+                         int32_t escape /* 0..255, or -1 = none */,
+                         uint32_t flags);
 
 /* FSST-style compressed string slot (SURVEY.md 8f row 3 "dict/FSST"):
  * rows hold code streams — code c < nsym expands to symbol bytes

@@ -72,6 +72,9 @@ def host():
         lib.sdb_host_blob_free.restype = None
         lib.sdb_host_bm25_stats.restype = None
         lib.sdb_host_topk_select.restype = C.c_int
+        lib.sdb_host_like_prog_size.restype = C.c_uint64
+        lib.sdb_host_like_compile.restype = C.c_int
+        lib.sdb_host_like_match.restype = C.c_int
         _host = lib
     return _host
 
@@ -363,6 +366,47 @@ def bm25_stats(docs_with_field, docs_with_term, total_term_freq, k=1.2,
     return idf.value, nc.value, nl.value
 
 
+def _like_bytes(x):
+    return x.encode() if isinstance(x, str) else bytes(x or b"")
+
+
+def _like_escape(escape):
+    """None -> -1; a one-byte str / bytes -> its byte; an int as it is (the
+    library rejects what lies outside -1..255)"""
+    if escape is None:
+        return -1
+    if isinstance(escape, int):
+        return escape
+    e = _like_bytes(escape)
+    if len(e) != 1:
+        raise ValueError("escape must be one byte")
+    return e[0]
+
+
+def like_compile(pattern, escape=None):
+    """Compile a byte-wise LIKE pattern (include/sdb_gpu.h
+    sdb_gpu_strpred_like) on the host into the program the GPU kernels run:
+    an opaque bytes object for like_match. str patterns are UTF-8 encoded.
+    Raises RuntimeError naming the return code on a rejected pattern."""
+    h = host()
+    pat = _like_bytes(pattern)
+    prog = C.create_string_buffer(h.sdb_host_like_prog_size())
+    pa = (C.c_uint8 * max(len(pat), 1))(*pat)
+    rc = h.sdb_host_like_compile(pa, C.c_uint32(len(pat)),
+                                 C.c_int32(_like_escape(escape)), prog)
+    if rc != 0:
+        raise RuntimeError(f"sdb_host_like_compile rc={rc}")
+    return prog.raw
+
+
+def like_match(prog, value):
+    """one value (bytes, or str as UTF-8) against a like_compile program,
+    with the matcher the GPU kernels share"""
+    v = _like_bytes(value)
+    va = (C.c_uint8 * max(len(v), 1)).from_buffer_copy(v or b"\0")
+    return bool(host().sdb_host_like_match(prog, va, C.c_uint64(len(v))))
+
+
 # ---------------------------------------------------------------------------
 # GPU library (the product query path; requires a GPU at call time)
 # ---------------------------------------------------------------------------
@@ -385,6 +429,9 @@ def gpu():
             "sdb_gpu_execute_topk_batch", "sdb_gpu_table_attach_validity",
             "sdb_gpu_execute_match_docs", "sdb_gpu_execute_count",
             "sdb_gpu_scan_topn", "sdb_gpu_table_gather",
+            "sdb_gpu_table_attach_strcol",
+            "sdb_gpu_table_attach_strcol_fsst", "sdb_gpu_strpred_mask",
+            "sdb_gpu_strpred_mask_ex", "sdb_gpu_strpred_like",
         ):
             getattr(lib, f).restype = C.c_int
         _gpu = lib
@@ -834,24 +881,54 @@ class GpuContext:
         if rc != 0:
             raise RuntimeError(f"attach_strcol_fsst rc={rc}")
 
-    STR_OPS = {"lt": 1, "ge": 2, "between": 3, "eq": 4, "prefix": 8}
+    STR_OPS = {"lt": 1, "ge": 2, "between": 3, "eq": 4, "prefix": 8,
+               "suffix": 9, "contains": 10}
+    # SDB_STRPRED_AND / _OR by name; an int passes through as the bits
+    STR_COMBINE = {"set": 0, "and": 2, "or": 4}
 
-    def strpred_mask(self, tab, slot, op, lo, hi=None):
+    def _strpred_flags(self, negate, combine):
+        c = self.STR_COMBINE[combine] if isinstance(combine, str) \
+            else int(combine)
+        return C.c_uint32(c | (1 if negate else 0))
+
+    def strpred_mask(self, tab, slot, op, lo, hi=None, negate=False,
+                     combine="set"):
         """Evaluate a string predicate over an attached raw string slot
         into its device row bitmask (memcmp order on UTF-8 bytes). op:
-        "lt"/"ge"/"between"/"eq"/"prefix" or the numeric SdbPredOp. The
-        mask is then consumed by scan_agg / scan_agg_hash via the pred
-        tuple (slot, 7, 0, 0)  [op 7 = SDB_PRED_STRMASK]."""
+        "lt"/"ge"/"between"/"eq"/"prefix"/"suffix"/"contains" or the
+        numeric SdbPredOp. negate inverts the result (NOT); combine "and" /
+        "or" folds it into the slot's current mask instead of replacing it
+        ("set"). The mask is then consumed by scan_agg / scan_agg_hash via
+        the pred tuple (slot, 7, 0, 0)  [op 7 = SDB_PRED_STRMASK]."""
         opn = self.STR_OPS[op] if isinstance(op, str) else int(op)
         lob = lo.encode() if isinstance(lo, str) else bytes(lo or b"")
         hib = hi.encode() if isinstance(hi, str) else bytes(hi or b"")
         la = (C.c_uint8 * max(len(lob), 1))(*lob)
         ha = (C.c_uint8 * max(len(hib), 1))(*hib)
-        rc = self._lib.sdb_gpu_strpred_mask(
+        rc = self._lib.sdb_gpu_strpred_mask_ex(
             self._ctx, tab, C.c_uint32(slot), C.c_int(opn), la,
-            C.c_uint32(len(lob)), ha, C.c_uint32(len(hib)))
+            C.c_uint32(len(lob)), ha, C.c_uint32(len(hib)),
+            self._strpred_flags(negate, combine))
         if rc != 0:
             raise RuntimeError(f"strpred_mask rc={rc}")
+
+    def strpred_like(self, tab, slot, pattern, escape=None, negate=False,
+                     combine="set"):
+        """Evaluate a byte-wise LIKE pattern (str, UTF-8 encoded, or bytes)
+        over a raw or FSST string slot into its row bitmask: '%' matches any
+        byte sequence, `escape` (one byte, or None) makes the next byte
+        literal, every other byte is literal; an unescaped '_' is rejected
+        (include/sdb_gpu.h sdb_gpu_strpred_like). negate / combine as in
+        strpred_mask. Raises RuntimeError naming the return code on a
+        rejected pattern; the slot's mask is then untouched."""
+        pat = _like_bytes(pattern)
+        pa = (C.c_uint8 * max(len(pat), 1))(*pat)
+        rc = self._lib.sdb_gpu_strpred_like(
+            self._ctx, tab, C.c_uint32(slot), pa, C.c_uint32(len(pat)),
+            C.c_int32(_like_escape(escape)),
+            self._strpred_flags(negate, combine))
+        if rc != 0:
+            raise RuntimeError(f"strpred_like rc={rc}")
 
     # SdbAggOp (include/sdb_gpu.h) by name; every (col, op) aggregate pair
     # takes the name or the number

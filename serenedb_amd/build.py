@@ -14,6 +14,8 @@ REPO = os.path.dirname(PKG)
 HOST_SRC = os.path.join(PKG, "csrc", "host", "sdb_host.cpp")
 GPU_SRC = os.path.join(PKG, "csrc", "hip", "sdb_gpu.hip")
 SCAN_SRC = os.path.join(PKG, "csrc", "hip", "sdb_scan.hip")
+# the LIKE matcher shared by the host library and the string kernels
+LIKE_HDR = os.path.join(PKG, "csrc", "sdb_like.h")
 HOST_SO = os.path.join(PKG, "libsdb_host.so")
 GPU_SO = os.path.join(PKG, "libsdb_gpu.so")
 
@@ -32,10 +34,10 @@ def build(force=False, verbose=True):
             print("+", " ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
 
-    if force or _newer(HOST_SRC, HOST_SO):
+    if force or _newer(HOST_SRC, HOST_SO) or _newer(LIKE_HDR, HOST_SO):
         run(HOST_CMD)
     gpu_srcs = [GPU_SRC] + ([SCAN_SRC] if os.path.exists(SCAN_SRC) else [])
-    if force or any(_newer(s, GPU_SO) for s in gpu_srcs):
+    if force or any(_newer(s, GPU_SO) for s in gpu_srcs + [LIKE_HDR]):
         run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
              "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-result"]
             + gpu_srcs + ["-o", GPU_SO])

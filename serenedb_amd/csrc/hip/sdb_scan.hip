@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../../include/sdb_gpu.h"
+#include "../sdb_like.h"
 #include "sdb_internal.h"
 
 #ifndef SCAN_NTHREADS
@@ -77,7 +78,9 @@ struct ColRef {
 };
 
 #define SDB_MAX_STRCOLS 4
+#ifndef SDB_STRLIT_MAX
 #define SDB_STRLIT_MAX 63  // literal bytes per side in strpred_mask
+#endif
 
 struct SdbGpuTable {
   void* cols[16];        // raw device array or whole FoR blob
@@ -116,6 +119,9 @@ struct SdbGpuTable {
   uint16_t str_nsym[SDB_MAX_STRCOLS];
   uint16_t str_symoff[SDB_MAX_STRCOLS][256];   // byte offsets, nsym+1 used
   uint8_t str_syms[SDB_MAX_STRCOLS][2048];
+  // the compiled pattern of the running SUFFIX / CONTAINS / LIKE call
+  // (sdb_like.h), allocated at the first such call
+  SdbLikeProg* like_prog;
 };
 
 // load-time min/max reduction over a raw i64 column. Signed order via the
@@ -1825,6 +1831,7 @@ static void table_free_str(SdbGpuTable* tab) {
     if (tab->str_blob[k]) (void)hipFree(tab->str_blob[k]);
     if (tab->str_mask[k]) (void)hipFree(tab->str_mask[k]);
   }
+  if (tab->like_prog) (void)hipFree(tab->like_prog);
 }
 
 static void table_free_partial(SdbGpuTable* tab) {
@@ -2001,7 +2008,11 @@ int sdb_gpu_table_attach_strcol(SdbGpuCtx* ctx, SdbGpuTable* tab,
   HIP_CHECK(hipMalloc(&tab->str_off[slot], 8 * (tab->rows + 1)));
   HIP_CHECK(hipMemcpy(tab->str_off[slot], offsets, 8 * (tab->rows + 1),
                       hipMemcpyHostToDevice));
-  HIP_CHECK(hipMalloc(&tab->str_blob[slot], blob_len ? blob_len : 1));
+  // the blob is padded to a multiple of 16 bytes (zero-filled): the
+  // cooperative substring kernel reads it in aligned 16-byte vectors
+  const uint64_t blob_pad = (blob_len + 16) & ~15ull;
+  HIP_CHECK(hipMalloc(&tab->str_blob[slot], blob_pad));
+  HIP_CHECK(hipMemset(tab->str_blob[slot] + (blob_pad - 16), 0, 16));
   if (blob_len)
     HIP_CHECK(hipMemcpy(tab->str_blob[slot], blob, blob_len,
                         hipMemcpyHostToDevice));
@@ -2018,8 +2029,26 @@ struct StrPredArgs {
   unsigned long long* mask;
   uint32_t op;
   uint32_t lo_len, hi_len;
+  uint32_t flags;  // SDB_STRPRED_*
   uint8_t lo[SDB_STRLIT_MAX + 1], hi[SDB_STRLIT_MAX + 1];
 };
+
+// The last step of every string-predicate kernel: one mask word per wave of
+// 64 consecutive rows. wf = the row exists and is well formed; NEGATE
+// inverts such rows only, so a malformed row and the bits at rows >= rows
+// stay 0. The word replaces the slot's old one, or is AND-ed / OR-ed into it.
+// With flags 0 this is the plain ballot store.
+__device__ __forceinline__ void strmask_store(unsigned long long* mask,
+                                              uint64_t r, bool wf, bool m,
+                                              uint32_t flags) {
+  const bool neg = (flags & SDB_STRPRED_NEGATE) != 0;
+  unsigned long long w = __ballot(wf && (m != neg));
+  if ((threadIdx.x & 63u) == 0) {
+    if (flags & SDB_STRPRED_AND) w &= mask[r >> 6];
+    else if (flags & SDB_STRPRED_OR) w |= mask[r >> 6];
+    mask[r >> 6] = w;
+  }
+}
 
 // lexicographic compare, memcmp order on unsigned bytes
 __device__ __forceinline__ int str_cmp_dev(const uint8_t* s, uint32_t n,
@@ -2057,8 +2086,7 @@ __global__ void strpred_kernel(StrPredArgs a) {
         }
       }
     }
-    const unsigned long long w = __ballot(m);
-    if ((threadIdx.x & 63u) == 0) a.mask[r >> 6] = w;
+    strmask_store(a.mask, r, r < a.rows, m, a.flags);
   }
 }
 
@@ -2108,10 +2136,10 @@ __global__ void strpred_fsst_kernel(StrPredFsstArgs fa) {
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
        r < rpad; r += stride) {
     bool m = false;
+    bool malformed = false;
     if (r < a.rows) {
       const uint64_t o0 = a.off[r], o1 = a.off[r + 1];
       FsstCmp clo{0, 0}, chi{0, 0};
-      bool malformed = false;
       for (uint64_t i = o0; i < o1; ++i) {
         const uint8_t c = a.blob[i];
         if (c == 255u) {  // escape: next byte is a literal
@@ -2146,16 +2174,291 @@ __global__ void strpred_fsst_kernel(StrPredFsstArgs fa) {
         }
       }
     }
-    const unsigned long long w = __ballot(m);
-    if ((threadIdx.x & 63u) == 0) a.mask[r >> 6] = w;
+    strmask_store(a.mask, r, r < a.rows && !malformed, m, a.flags);
   }
+}
+
+// ---- SUFFIX / CONTAINS / LIKE: the sdb_like.h program on the device ----
+// The compiled pattern (2.2 KB, too large to ride beside the FSST symbol
+// table in the kernel arguments) sits in device memory and is staged into
+// LDS once per block.
+
+struct StrLikeArgs {
+  const uint64_t* off;
+  const uint8_t* blob;
+  uint64_t rows;
+  unsigned long long* mask;
+  const SdbLikeProg* prog;
+  uint32_t flags;
+};
+
+static_assert(sizeof(SdbLikeProg) % 8 == 0, "staged as u64 words");
+__device__ __forceinline__ void like_prog_stage(SdbLikeProg* dst,
+                                                const SdbLikeProg* src) {
+  const uint64_t* s = reinterpret_cast<const uint64_t*>(src);
+  uint64_t* d = reinterpret_cast<uint64_t*>(dst);
+  for (uint32_t i = threadIdx.x; i < sizeof(SdbLikeProg) / 8; i += blockDim.x)
+    d[i] = s[i];
+}
+
+// row-wise automaton over a raw slot: one thread per row, any program
+__global__ void strlike_kernel(StrLikeArgs a) {
+  __shared__ SdbLikeProg sp;
+  like_prog_stage(&sp, a.prog);
+  __syncthreads();
+  const uint64_t rpad = (a.rows + 63) & ~63ull;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       r < rpad; r += stride) {
+    bool m = false;
+    if (r < a.rows) {
+      const uint64_t o0 = a.off[r], o1 = a.off[r + 1];
+      SdbLikeState st;
+      sdb_like_init(st);
+      // a raw row is decided as soon as the anchored first segment died or
+      // every segment matched with the end free
+      for (uint64_t i = o0; i < o1 && !st.fail && st.seg < sp.nseg; ++i)
+        sdb_like_feed(sp, st, a.blob[i]);
+      m = sdb_like_finish(sp, st, o1 - o0);
+    }
+    strmask_store(a.mask, r, r < a.rows, m, a.flags);
+  }
+}
+
+struct StrLikeFsstArgs {
+  StrLikeArgs base;
+  uint32_t nsym;
+  uint16_t symoff[256];
+  uint8_t syms[2048];
+};
+
+// the same over an FSST slot: decoded bytes go to the step one at a time.
+// Every code of a row is read, so a malformed row is seen whatever the
+// pattern decided before it.
+__global__ void strlike_fsst_kernel(StrLikeFsstArgs fa) {
+  __shared__ SdbLikeProg sp;
+  __shared__ uint8_t ssym[2048];
+  __shared__ uint16_t soff[256];
+  like_prog_stage(&sp, fa.base.prog);
+  for (uint32_t i = threadIdx.x; i < 2048; i += blockDim.x)
+    ssym[i] = fa.syms[i];
+  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x)
+    soff[i] = fa.symoff[i];
+  __syncthreads();
+  const StrLikeArgs a = fa.base;
+  const uint64_t rpad = (a.rows + 63) & ~63ull;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       r < rpad; r += stride) {
+    bool m = false;
+    bool malformed = false;
+    if (r < a.rows) {
+      const uint64_t o0 = a.off[r], o1 = a.off[r + 1];
+      SdbLikeState st;
+      sdb_like_init(st);
+      for (uint64_t i = o0; i < o1; ++i) {
+        const uint8_t c = a.blob[i];
+        if (c == 255u) {  // escape: next byte is a literal
+          if (++i >= o1) { malformed = true; break; }
+          sdb_like_feed(sp, st, a.blob[i]);
+        } else {
+          if (c >= fa.nsym) { malformed = true; break; }
+          for (uint32_t j = soff[c]; j < (uint32_t)soff[c + 1]; ++j)
+            sdb_like_feed(sp, st, ssym[j]);
+        }
+      }
+      if (!malformed) m = sdb_like_finish(sp, st, st.n);
+    }
+    strmask_store(a.mask, r, r < a.rows && !malformed, m, a.flags);
+  }
+}
+
+// Cooperative substring kernel: raw slot, one unanchored segment of m >= 1
+// bytes (CONTAINS, LIKE '%x%'). One wave (= one block) owns 64 consecutive
+// rows, whose bytes are the contiguous span [off[r0], off[r0 + 64]) of the
+// blob. It streams the span through LDS in STRLIKE_CHUNK-byte steps of
+// aligned 16-byte loads, keeping the last STRLIKE_CARRY >= m - 1 bytes of
+// a step in front of the next, so work follows the bytes and not the
+// longest row of the wave. Each step tests the start positions whose LAST
+// byte lies in the newly loaded bytes, so every position is tested once. A
+// hit at blob position p belongs to the row found by binary search in the 65
+// staged offsets, and counts only if p + m <= off[row + 1]: a match never
+// straddles rows. Loads start at 16-byte multiples below the end of the
+// span; the blob allocation is padded to a multiple of 16 bytes
+// (sdb_gpu_table_attach_strcol), so none leaves it.
+#define STRLIKE_CHUNK 4096u  // a power of two, at most 8192
+#define STRLIKE_CARRY 64u
+
+struct StrLikeCoopArgs {
+  StrLikeArgs base;
+  uint32_t m;
+  uint8_t lit[64];
+};
+
+__global__ void __launch_bounds__(64) strlike_coop_kernel(StrLikeCoopArgs ca) {
+  __shared__ uint4 sbuf4[(STRLIKE_CARRY + STRLIKE_CHUNK) / 16];
+  __shared__ uint64_t soff[65];
+  __shared__ unsigned long long sword;
+  __shared__ uint8_t slit[64];
+  uint8_t* sbuf = reinterpret_cast<uint8_t*>(sbuf4);
+  const StrLikeArgs a = ca.base;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t m = ca.m;
+  slit[lane] = ca.lit[lane];
+  const uint8_t l0 = ca.lit[0];
+  const uint64_t nwin = (a.rows + 63) / 64;
+  for (uint64_t w = blockIdx.x; w < nwin; w += gridDim.x) {
+    const uint64_t r0 = w * 64;
+    const uint32_t nr = a.rows - r0 < 64 ? (uint32_t)(a.rows - r0) : 64u;
+    __syncthreads();  // the previous window is stored
+    soff[lane] = a.off[r0 + (lane < nr ? lane : nr)];
+    if (lane == 0) {
+      soff[64] = a.off[r0 + nr];
+      sword = 0;
+    }
+    __syncthreads();
+    const uint64_t b0 = soff[0], b1 = soff[64];
+    if (b1 - b0 >= m) {
+      for (uint64_t cs = b0 & ~15ull; cs < b1; cs += STRLIKE_CHUNK) {
+        // carry the tail of the last step over, then load this one; before
+        // the first step the carried bytes lie below b0 and are never used
+        const uint8_t carry = sbuf[STRLIKE_CHUNK + lane];
+        __syncthreads();
+        sbuf[lane] = carry;
+        for (uint32_t v = lane; v < STRLIKE_CHUNK / 16; v += 64) {
+          const uint64_t at = cs + (uint64_t)v * 16;
+          if (at < b1)
+            sbuf4[STRLIKE_CARRY / 16 + v] =
+              *reinterpret_cast<const uint4*>(a.blob + at);
+        }
+        __syncthreads();
+        // start position p = cs + j - (m - 1) sits at sbuf[i]; j runs over
+        // b0 <= p and p + m <= b1, i.e. b0 + m - 1 <= cs + j < b1
+        const uint32_t jlo =
+          cs < b0 + (m - 1) ? (uint32_t)(b0 + (m - 1) - cs) : 0u;
+        const uint32_t jhi =
+          b1 - cs < STRLIKE_CHUNK ? (uint32_t)(b1 - cs) : STRLIKE_CHUNK;
+        for (uint32_t j = jlo + lane; j < jhi; j += 64) {
+          const uint32_t i = STRLIKE_CARRY - (m - 1) + j;
+          if (sbuf[i] != l0) continue;
+          bool hit = true;
+          for (uint32_t k = 1; k < m && hit; ++k) hit = sbuf[i + k] == slit[k];
+          if (!hit) continue;
+          const uint64_t p = cs + j - (m - 1);
+          uint32_t lo = 0, hi = nr;  // soff[lo] <= p < soff[hi]
+          while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (soff[mid] <= p) lo = mid; else hi = mid;
+          }
+          if (p + m <= soff[lo + 1]) atomicOr(&sword, 1ull << lo);
+        }
+      }
+    }
+    __syncthreads();
+    if (lane == 0) {
+      unsigned long long wv = sword;
+      if (a.flags & SDB_STRPRED_NEGATE)
+        wv = ~wv & (nr == 64 ? ~0ull : (1ull << nr) - 1ull);
+      if (a.flags & SDB_STRPRED_AND) wv &= a.mask[w];
+      else if (a.flags & SDB_STRPRED_OR) wv |= a.mask[w];
+      a.mask[w] = wv;
+    }
+  }
+}
+
+// flags and slot checks shared by the three entries, before any launch
+static int strpred_check(const SdbGpuCtx* ctx, const SdbGpuTable* tab,
+                         uint32_t slot, uint32_t flags) {
+  if (!ctx || !tab || slot >= SDB_MAX_STRCOLS || !tab->str_off[slot])
+    return SDB_ERR_INVALID;
+  if (flags & ~(SDB_STRPRED_NEGATE | SDB_STRPRED_AND | SDB_STRPRED_OR))
+    return SDB_ERR_INVALID;
+  const uint32_t comb = flags & (SDB_STRPRED_AND | SDB_STRPRED_OR);
+  if (comb == (SDB_STRPRED_AND | SDB_STRPRED_OR)) return SDB_ERR_INVALID;
+  if (comb && !tab->str_mask_set[slot]) return SDB_ERR_INVALID;
+  return SDB_OK;
+}
+
+static int strlike_run(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t slot,
+                       const SdbLikeProg& prog, uint32_t flags) {
+  if (!tab->like_prog)
+    HIP_CHECK(hipMalloc(&tab->like_prog, sizeof(SdbLikeProg)));
+  HIP_CHECK(hipMemcpy(tab->like_prog, &prog, sizeof(prog),
+                      hipMemcpyHostToDevice));
+  StrLikeArgs a{};
+  a.off = tab->str_off[slot];
+  a.blob = tab->str_blob[slot];
+  a.rows = tab->rows;
+  a.mask = tab->str_mask[slot];
+  a.prog = tab->like_prog;
+  a.flags = flags;
+  const uint32_t nb =
+    (uint32_t)std::min<uint64_t>(4096, (tab->rows + 255) / 256);
+  // the cooperative kernel takes the substring shape on a raw slot; the
+  // SDB_LIKE_ROWWISE test hook (sdb_gpu.h) keeps it on the row-wise one
+  bool coop = !tab->str_fsst[slot] && prog.nseg == 1 &&
+              !prog.anchored_start && !prog.anchored_end;
+  if (coop)
+    if (const char* e = std::getenv("SDB_LIKE_ROWWISE"))
+      if (std::strtoul(e, nullptr, 10) == 1) coop = false;
+  if (tab->str_fsst[slot]) {
+    StrLikeFsstArgs fa{};
+    fa.base = a;
+    fa.nsym = tab->str_nsym[slot];
+    std::memcpy(fa.symoff, tab->str_symoff[slot], sizeof(fa.symoff));
+    std::memcpy(fa.syms, tab->str_syms[slot], sizeof(fa.syms));
+    hipLaunchKernelGGL(strlike_fsst_kernel, dim3(nb ? nb : 1), dim3(256), 0,
+                       ctx->stream, fa);
+  } else if (coop) {
+    StrLikeCoopArgs ca{};
+    ca.base = a;
+    ca.m = prog.lit_len;
+    std::memcpy(ca.lit, prog.lit, sizeof(ca.lit));
+    const uint32_t nw =
+      (uint32_t)std::min<uint64_t>(8192, (tab->rows + 63) / 64);
+    hipLaunchKernelGGL(strlike_coop_kernel, dim3(nw ? nw : 1), dim3(64), 0,
+                       ctx->stream, ca);
+  } else {
+    hipLaunchKernelGGL(strlike_kernel, dim3(nb ? nb : 1), dim3(256), 0,
+                       ctx->stream, a);
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  tab->str_mask_set[slot] = 1;
+  return SDB_OK;
+}
+
+int sdb_gpu_strpred_like(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t slot,
+                         const uint8_t* pattern, uint32_t pattern_len,
+                         int32_t escape, uint32_t flags) {
+  const int rc = strpred_check(ctx, tab, slot, flags);
+  if (rc) return rc;
+  SdbLikeProg prog;
+  if (sdb_like_compile(pattern, pattern_len, escape, &prog))
+    return SDB_ERR_INVALID;
+  return strlike_run(ctx, tab, slot, prog, flags);
 }
 
 int sdb_gpu_strpred_mask(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t slot,
                          SdbPredOp op, const uint8_t* lo, uint32_t lo_len,
                          const uint8_t* hi, uint32_t hi_len) {
-  if (!ctx || !tab || slot >= SDB_MAX_STRCOLS || !tab->str_off[slot])
-    return SDB_ERR_INVALID;
+  return sdb_gpu_strpred_mask_ex(ctx, tab, slot, op, lo, lo_len, hi, hi_len,
+                                 0);
+}
+
+int sdb_gpu_strpred_mask_ex(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t slot,
+                            SdbPredOp op, const uint8_t* lo, uint32_t lo_len,
+                            const uint8_t* hi, uint32_t hi_len,
+                            uint32_t flags) {
+  const int rc = strpred_check(ctx, tab, slot, flags);
+  if (rc) return rc;
+  if (op == SDB_PRED_SUFFIX || op == SDB_PRED_CONTAINS) {
+    if (lo_len > SDB_STRLIT_MAX || (lo_len && !lo)) return SDB_ERR_INVALID;
+    SdbLikeProg prog;
+    if (sdb_like_literal(lo, lo_len, false, op == SDB_PRED_SUFFIX, &prog))
+      return SDB_ERR_INVALID;
+    return strlike_run(ctx, tab, slot, prog, flags);
+  }
   if (op != SDB_PRED_LT && op != SDB_PRED_GE && op != SDB_PRED_BETWEEN &&
       op != SDB_PRED_EQ && op != SDB_PRED_PREFIX)
     return SDB_ERR_INVALID;
@@ -2164,6 +2467,7 @@ int sdb_gpu_strpred_mask(SdbGpuCtx* ctx, SdbGpuTable* tab, uint32_t slot,
   if ((lo_len && !lo) || (hi_len && !hi)) return SDB_ERR_INVALID;
   if (op == SDB_PRED_BETWEEN && !hi && hi_len) return SDB_ERR_INVALID;
   StrPredArgs a{};
+  a.flags = flags;
   a.off = tab->str_off[slot];
   a.blob = tab->str_blob[slot];
   a.rows = tab->rows;

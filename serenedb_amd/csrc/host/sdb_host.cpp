@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../../include/sdb_format.h"
+#include "../sdb_like.h"
 
 namespace {
 
@@ -971,6 +972,26 @@ int sdb_host_topk_select(const SdbScoreDocC* cands, uint64_t n, uint32_t k,
   std::copy(v.begin(), v.begin() + kk, out);
   *out_count = uint32_t(kk);
   return 0;
+}
+
+// Byte-wise LIKE (include/sdb_gpu.h sdb_gpu_strpred_like): the compiler and
+// the matcher the GPU string kernels run (../sdb_like.h), on the host. prog
+// points at sdb_host_like_prog_size() bytes; a rejected pattern returns -1
+// and leaves them untouched.
+uint64_t sdb_host_like_prog_size(void) { return sizeof(SdbLikeProg); }
+
+int sdb_host_like_compile(const uint8_t* pattern, uint32_t len,
+                          int32_t escape, void* prog) {
+  SdbLikeProg p;
+  const int rc = sdb_like_compile(pattern, len, escape, &p);
+  if (rc == 0 && prog) std::memcpy(prog, &p, sizeof(p));
+  return prog ? rc : -1;
+}
+
+int sdb_host_like_match(const void* prog, const uint8_t* s, uint64_t n) {
+  SdbLikeProg p;
+  std::memcpy(&p, prog, sizeof(p));  // the caller's buffer may be unaligned
+  return sdb_like_match(p, s, n) ? 1 : 0;
 }
 
 }  // extern "C"
