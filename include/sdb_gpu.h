@@ -51,6 +51,11 @@ extern "C" {
 #define SDB_ERR_OOM (-4)
 #define SDB_ERR_BAD_SEGMENT (-5)
 #define SDB_ERR_COLLISION (-6) /* sdb_gpu_scan_agg_hash_multi: see there */
+/* Every sdb_gpu_table_* / sdb_gpu_strpred_* / sdb_gpu_scan_* entry maps a
+ * failed device call the same way: no device -> SDB_ERR_NO_GPU, a failed
+ * device allocation -> SDB_ERR_OOM (the attach, string-predicate, string-key
+ * and gather entries too, which once answered SDB_ERR_HIP for it), anything
+ * else -> SDB_ERR_HIP. */
 
 /* mirrors irs::ScoreDoc: {score_t score; doc_id_t doc; uint32_t segment_idx}
  * (index/iterators.hpp:93-99) */
