@@ -113,6 +113,14 @@ typedef struct SdbTermEntry {
 
 #define SDB_SEG_MAGIC 0x3130444D41424453ull /* "SDBAMD01" */
 
+/* Zero bytes the builder leaves behind the payload section (before 64-byte
+ * rounding of the blob). Decoders fetch packed words through aligned,
+ * branch-free loads that touch up to 20 bytes past the end of a stream (the
+ * derivation is next to SDB_FETCH_OVERREAD in sdb_gpu.hip, which asserts
+ * that this pad covers it); for the last stream of the segment those bytes
+ * are this pad. */
+#define SDB_PAYLOAD_TAIL_PAD 64u
+
 /* Serialized segment header. All section offsets are bytes from the start of
  * the blob; every section start is 64-byte aligned. The whole blob is the
  * "mmap-equivalent byte span" handed across the C ABI (cf. the reference's

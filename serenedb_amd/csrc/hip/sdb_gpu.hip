@@ -97,30 +97,86 @@ struct SdbGpuSegment {
 // ---------------------------------------------------------------------------
 // kernel helpers
 // ---------------------------------------------------------------------------
+// Payload fetch. Blocks start at arbitrary bytes, so every value is read
+// through 4-byte-aligned words and shifted into place. Two rules keep a
+// whole block's loads in ONE memory round trip:
+//   * the aligned pointer is derived by pointer arithmetic from the incoming
+//     pointer (never through an integer round trip), so address-space
+//     inference survives and the loads are global_load_*, not FLAT — FLAT
+//     loads count in lgkmcnt as well as vmcnt and so serialise against every
+//     LDS wait nearby;
+//   * no load depends on data or on the byte residue: the neighbour word is
+//     always read and a funnel shift picks the bytes, so the compiler is
+//     free to issue every load of every stream before the first wait.
+//
+// Over-read bound. A bitpacked stream is 1 tag byte + 16*bits payload bytes
+// (bits rows of four 32-bit words). packed_pair_load reads the value's row w
+// and, unconditionally, row w+1; w <= bits-1, so the furthest word starts
+// at payload byte 16*bits + 12 (column 3 of the row after the last). An
+// unaligned word at address x is read from the aligned 8-byte window that
+// starts at x - (x & 3) and ends at most at x + 8. The furthest byte touched
+// is therefore payload byte 16*bits + 20: at most 20 bytes past the end of
+// the stream (SDB_FETCH_OVERREAD). The other users stay below that:
+// ld_u32_un touches 4 bytes past its word, ld_u64_un 4 past its 8, and
+// ld_u32_uniform 3 past a 1-byte all-same value. Below the pointer at
+// most 3 bytes are touched, which stay inside the (aligned) allocation.
+// For every stream but the last of the segment the extra bytes are the
+// next stream's; for the last they are the pad that sdb_gpu_segment_load
+// allocates behind the device payload (SDB_DEV_PAYLOAD_PAD), and the blob
+// itself carries SDB_PAYLOAD_TAIL_PAD for host-side readers of the same
+// shape.
+#define SDB_FETCH_OVERREAD 20u
+#define SDB_DEV_PAYLOAD_PAD 512u  // also covers the 512 B prefetch touches
+static_assert(SDB_FETCH_OVERREAD <= SDB_PAYLOAD_TAIL_PAD,
+              "blob tail pad must cover the decode over-read");
+static_assert(SDB_FETCH_OVERREAD <= SDB_DEV_PAYLOAD_PAD,
+              "device payload pad must cover the decode over-read");
+
+__device__ __forceinline__ const uint32_t* align_down4(const uint8_t* p) {
+  return (const uint32_t*)(p - ((uintptr_t)p & 3u));
+}
+
 __device__ __forceinline__ uint32_t ld_u32_un(const uint8_t* p) {
-  // aligned-pair unaligned read (payload blocks start at arbitrary bytes;
-  // blob has a 64 B tail pad so the +4 word is always in bounds)
-  const uintptr_t a = (uintptr_t)p;
-  const uint32_t* w = (const uint32_t*)(a & ~(uintptr_t)3);
-  const uint32_t sh = ((uint32_t)a & 3u) * 8u;
-  const uint32_t lo = w[0];
-  if (sh == 0) return lo;
-  const uint32_t hi = w[1];
-  return (lo >> sh) | (hi << (32 - sh));
+  const uint32_t* w = align_down4(p);
+  return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(uintptr_t)p & 3u);
+}
+
+// The same read for a WAVE-UNIFORM pointer (the one value of an all-same
+// block). ld_u32_un must not be used there: the compiler makes uniform
+// aligned-word loads scalar, and it may fold the caller's constant offset
+// into the instruction's immediate, leaving an unaligned base register —
+// `s_load_dwordx2 s[..], s[base], 0x1` — which the scalar unit does not add
+// up byte-exactly (on gfx950 it fetched the preceding word). Byte loads have
+// no scalar form, stay on the vector path and need no alignment.
+__device__ __forceinline__ uint32_t ld_u32_uniform(const uint8_t* p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) |
+         ((uint32_t)p[3] << 24);
 }
 
 __device__ __forceinline__ uint64_t ld_u64_un(const uint8_t* p) {
-  return (uint64_t)ld_u32_un(p) | ((uint64_t)ld_u32_un(p + 4) << 32);
+  const uint32_t* w = align_down4(p);
+  const uint32_t r = (uint32_t)(uintptr_t)p & 3u;
+  const uint32_t w1 = w[1];
+  return (uint64_t)__builtin_amdgcn_alignbyte(w1, w[0], r) |
+         ((uint64_t)__builtin_amdgcn_alignbyte(w[2], w1, r) << 32);
 }
 
-// inclusive wave-scan (64 lanes) of a uint32
+// inclusive wave-scan (64 lanes) of a uint32, on the VALU (DPP): row
+// shifts 1/2/4/8 scan each 16-lane row, then the two row broadcasts carry
+// row 0 -> 1 and 2 -> 3 (lane 15 of a row into the next row, row mask 0xA)
+// and rows 0-1 -> 2-3 (lane 31 into rows 2 and 3, row mask 0xC).
+// Lanes a step does not feed take the `old` operand, 0. No LDS crossbar
+// (ds_bpermute) and no lgkmcnt wait per step.
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t n = __shfl_up(v, off, 64);
-    if (lane >= off) v += n;
-  }
-  return v;
+  (void)lane;
+  int x = (int)v;
+  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);  // row_shr:1
+  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);  // row_shr:2
+  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false);  // row_shr:4
+  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false);  // row_shr:8
+  x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);  // bcast15
+  x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);  // bcast31
+  return (uint32_t)x;
 }
 
 // score -> histogram bin: the ONE bucketing function, used identically for
@@ -169,19 +225,57 @@ __device__ __forceinline__ void load_tags3(const uint8_t* p0,
   *t2 = __shfl(v, 2, 64);
 }
 
-// vertical-layout delta extract: value i of a 128-block, b bits
-// (simdcomp d1 layout — see include/sdb_format.h)
-__device__ __forceinline__ uint32_t extract_packed(const uint8_t* base,
-                                                   uint32_t bits,
-                                                   uint32_t i) {
-  const uint32_t mask = bits >= 32 ? 0xFFFFFFFFu : (1u << bits) - 1u;
-  const uint32_t c = i & 3u, g = i >> 2;
+// vertical-layout extract (simdcomp layout — see include/sdb_format.h):
+// value i of a 128-block of b-bit values sits in column c = i & 3, group
+// g = i >> 2, at bit g*b of that column's word stream; word w of column c
+// is at byte 16*w + 4*c. The value's word and the next word of the column
+// are both fetched unconditionally (no straddle branch); the funnel shift
+// ignores the high word when nothing straddles, and the mask is a select.
+//
+// Values 2*lane and 2*lane+1 of a 128-block: same group, neighbouring
+// columns, so the two share their aligned words — three words of row w and
+// three of row w+1 serve both (two 12-byte loads per stream per lane).
+// The fetch and the unpack are separate steps so that a caller decoding
+// several streams can issue every stream's loads first (packed_pair_load),
+// fence the schedule, and only then touch the data (packed_pair_get).
+struct PackedPair {
+  uint32_t a0, a1, a2;  // row w:   aligned words covering both columns
+  uint32_t b0, b1, b2;  // row w+1: the same columns
+  uint32_t r, sh, mask;
+};
+
+__device__ __forceinline__ PackedPair packed_pair_load(const uint8_t* base,
+                                                       uint32_t bits,
+                                                       int lane) {
+  PackedPair p;
+  p.mask = bits >= 32 ? 0xFFFFFFFFu : (1u << bits) - 1u;
+  const uint32_t c = (2u * (uint32_t)lane) & 3u, g = (uint32_t)lane >> 1;
   const uint32_t bit = g * bits;
-  const uint32_t w = bit >> 5, sh = bit & 31u;
-  uint64_t v = (uint64_t)ld_u32_un(base + 4u * (w * 4 + c)) >> sh;
-  if (sh + bits > 32)
-    v |= (uint64_t)ld_u32_un(base + 4u * ((w + 1) * 4 + c)) << (32 - sh);
-  return (uint32_t)v & mask;
+  const uint32_t w = bit >> 5;
+  p.sh = bit & 31u;
+  const uint8_t* q = base + 16u * w + 4u * c;
+  const uint32_t* a = align_down4(q);
+  p.r = (uint32_t)(uintptr_t)q & 3u;
+  p.a0 = a[0], p.a1 = a[1], p.a2 = a[2];
+  p.b0 = a[4], p.b1 = a[5], p.b2 = a[6];
+  return p;
+}
+
+__device__ __forceinline__ void packed_pair_get(const PackedPair& p,
+                                                uint32_t* v0, uint32_t* v1) {
+  const uint32_t lo0 = __builtin_amdgcn_alignbyte(p.a1, p.a0, p.r);
+  const uint32_t lo1 = __builtin_amdgcn_alignbyte(p.a2, p.a1, p.r);
+  const uint32_t hi0 = __builtin_amdgcn_alignbyte(p.b1, p.b0, p.r);
+  const uint32_t hi1 = __builtin_amdgcn_alignbyte(p.b2, p.b1, p.r);
+  *v0 = __builtin_amdgcn_alignbit(hi0, lo0, p.sh) & p.mask;
+  *v1 = __builtin_amdgcn_alignbit(hi1, lo1, p.sh) & p.mask;
+}
+
+__device__ __forceinline__ void extract_packed_pair(const uint8_t* base,
+                                                    uint32_t bits, int lane,
+                                                    uint32_t* v0,
+                                                    uint32_t* v1) {
+  packed_pair_get(packed_pair_load(base, bits, lane), v0, v1);
 }
 
 // Decode one doc block (ReadTailDelta, format_block_128.hpp:476-559) with
@@ -194,8 +288,8 @@ __device__ void decode_doc_block_wave(const uint8_t* p, uint32_t len,
     const uint32_t bits = tag - SDB_DE_DELTA_BITPACK_02 + 2;
     const uint8_t* base = p + 1;
     const uint32_t i0 = 2u * lane;
-    const uint32_t d0 = extract_packed(base, bits, i0);
-    const uint32_t d1 = extract_packed(base, bits, i0 + 1);
+    uint32_t d0, d1;
+    extract_packed_pair(base, bits, lane, &d0, &d1);
     const uint32_t pair = d0 + d1;
     const uint32_t incl = wave_incl_scan(pair, lane);
     const uint32_t excl = incl - pair;
@@ -215,7 +309,7 @@ __device__ void decode_doc_block_wave(const uint8_t* p, uint32_t len,
       const uint32_t nb = tag == SDB_DE_DELTA_ALL_SAME_08
                             ? 1u
                             : (tag == SDB_DE_DELTA_ALL_SAME_16 ? 2u : 4u);
-      uint32_t v = ld_u32_un(p + 1);
+      uint32_t v = ld_u32_uniform(p + 1);
       if (nb < 4) v &= (1u << (8 * nb)) - 1u;
       // FillSameDelta: out[i] = prev + v + v*i
       for (uint32_t i = lane; i < len; i += 64)
@@ -285,8 +379,10 @@ __device__ void decode_freq_block_wave(const uint8_t* p, uint32_t len,
     const uint32_t bits = tag - SDB_E_BITPACK_01 + 1;
     const uint8_t* base = p + 1;
     const uint32_t i0 = 2u * lane;
-    scratch[i0] = extract_packed(base, bits, i0);
-    scratch[i0 + 1] = extract_packed(base, bits, i0 + 1);
+    uint32_t v0, v1;
+    extract_packed_pair(base, bits, lane, &v0, &v1);
+    scratch[i0] = v0;
+    scratch[i0 + 1] = v1;
     return;
   }
   switch (tag) {
@@ -300,7 +396,7 @@ __device__ void decode_freq_block_wave(const uint8_t* p, uint32_t len,
     case SDB_E_ALL_SAME_32: {
       const uint32_t nb =
         tag == SDB_E_ALL_SAME_08 ? 1u : (tag == SDB_E_ALL_SAME_16 ? 2u : 4u);
-      uint32_t v = ld_u32_un(p + 1);
+      uint32_t v = ld_u32_uniform(p + 1);
       if (nb < 4) v &= (1u << (8 * nb)) - 1u;
       for (uint32_t i = lane; i < len; i += 64) scratch[i] = v;
       break;
@@ -369,7 +465,10 @@ __device__ __forceinline__ void swin_add(float* swin, uint32_t off,
 // during the PREVIOUS window's phases so next window's first-block decode
 // reads LDS instead of riding an exposed HBM round trip.
 #define SDB_STG_TERMS 4
-#define SDB_STG_CAP 352  // 22 x 16 B; fused span 3+16*(db+fb+nb) + align pad
+// 22 x 16 B. A block is staged only when align pad + fused span
+// 3+16*(db+fb+nb) + SDB_FETCH_OVERREAD fits, so the decode's over-read
+// stays inside the slot (its bytes past the span are stale and masked off)
+#define SDB_STG_CAP 352
 #endif
 
 template <int LEAN>
@@ -390,14 +489,17 @@ __device__ __forceinline__ bool try_block_fused(
   const uint8_t* db = db0;
   const uint8_t* fb = db0 + (d.freq_off - d.doc_off);
   const uint8_t* nb = fb + 1 + 16u * fbits;  // bitpack size = 1 + 16*bits
-  const uint32_t i0 = 2u * lane, i1 = i0 + 1;
-  // all loads issue here, before any cross-lane dependency
-  const uint32_t dd0 = extract_packed(db + 1, dbits, i0);
-  const uint32_t dd1 = extract_packed(db + 1, dbits, i1);
-  const uint32_t f0 = extract_packed(fb + 1, fbits, i0);
-  const uint32_t f1 = extract_packed(fb + 1, fbits, i1);
-  const uint32_t n0 = extract_packed(nb + 1, nbits, i0);
-  const uint32_t n1 = extract_packed(nb + 1, nbits, i1);
+  // six 12-byte loads, none depending on another's data: the compiled
+  // code issues all of them before the first wait ("One round
+  // trip per block")
+  const PackedPair pd = packed_pair_load(db + 1, dbits, lane);
+  const PackedPair pf = packed_pair_load(fb + 1, fbits, lane);
+  const PackedPair pn = packed_pair_load(nb + 1, nbits, lane);
+  __builtin_amdgcn_sched_barrier(0);  // no unpack hoists above a load
+  uint32_t dd0, dd1, f0, f1, n0, n1;
+  packed_pair_get(pd, &dd0, &dd1);
+  packed_pair_get(pf, &f0, &f1);
+  packed_pair_get(pn, &n0, &n1);
   (void)norms_col;
   const uint32_t pair = dd0 + dd1;
   const uint32_t incl = wave_incl_scan(pair, lane);
@@ -444,33 +546,28 @@ __device__ __forceinline__ bool try_block_fused2(
   const uint8_t* bdoc = pl + db_.doc_off;
   const uint8_t* bfrq = pl + db_.freq_off;
   const uint8_t* bnrm = bfrq + 1 + 16u * bfb;
-  const uint32_t i0 = 2u * lane, i1 = i0 + 1;
-  // every load issues here — no tag fetch precedes them
-  const uint32_t a_d0 = extract_packed(adoc + 1, adb, i0);
-  const uint32_t a_d1 = extract_packed(adoc + 1, adb, i1);
-  const uint32_t b_d0 = extract_packed(bdoc + 1, bdb, i0);
-  const uint32_t b_d1 = extract_packed(bdoc + 1, bdb, i1);
-  const uint32_t a_f0 = extract_packed(afrq + 1, afb, i0);
-  const uint32_t a_f1 = extract_packed(afrq + 1, afb, i1);
-  const uint32_t b_f0 = extract_packed(bfrq + 1, bfb, i0);
-  const uint32_t b_f1 = extract_packed(bfrq + 1, bfb, i1);
-  const uint32_t a_n0 = extract_packed(anrm + 1, anb, i0);
-  const uint32_t a_n1 = extract_packed(anrm + 1, anb, i1);
-  const uint32_t b_n0 = extract_packed(bnrm + 1, bnb, i0);
-  const uint32_t b_n1 = extract_packed(bnrm + 1, bnb, i1);
-  // two independent wave scans (shfl chains interleave)
+  // twelve 12-byte loads, no tag fetch before them and none depending on
+  // another's data: all issue before the first wait
+  const PackedPair pad = packed_pair_load(adoc + 1, adb, lane);
+  const PackedPair pbd = packed_pair_load(bdoc + 1, bdb, lane);
+  const PackedPair paf = packed_pair_load(afrq + 1, afb, lane);
+  const PackedPair pbf = packed_pair_load(bfrq + 1, bfb, lane);
+  const PackedPair pan = packed_pair_load(anrm + 1, anb, lane);
+  const PackedPair pbn = packed_pair_load(bnrm + 1, bnb, lane);
+  __builtin_amdgcn_sched_barrier(0);  // no unpack hoists above a load
+  uint32_t a_d0, a_d1, b_d0, b_d1, a_f0, a_f1, b_f0, b_f1;
+  uint32_t a_n0, a_n1, b_n0, b_n1;
+  packed_pair_get(pad, &a_d0, &a_d1);
+  packed_pair_get(pbd, &b_d0, &b_d1);
+  packed_pair_get(paf, &a_f0, &a_f1);
+  packed_pair_get(pbf, &b_f0, &b_f1);
+  packed_pair_get(pan, &a_n0, &a_n1);
+  packed_pair_get(pbn, &b_n0, &b_n1);
+  // two independent wave scans (the DPP chains interleave)
   const uint32_t a_pair = a_d0 + a_d1;
   const uint32_t b_pair = b_d0 + b_d1;
-  uint32_t a_incl = a_pair, b_incl = b_pair;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t an = __shfl_up(a_incl, off, 64);
-    const uint32_t bn = __shfl_up(b_incl, off, 64);
-    if (lane >= off) {
-      a_incl += an;
-      b_incl += bn;
-    }
-  }
+  const uint32_t a_incl = wave_incl_scan(a_pair, lane);
+  const uint32_t b_incl = wave_incl_scan(b_pair, lane);
   const uint32_t a_excl = a_incl - a_pair;
   const uint32_t b_excl = b_incl - b_pair;
   const uint32_t docs[4] = {da.prev_doc + a_excl + a_d0,
@@ -802,8 +899,7 @@ void topk_window_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
                                       ? dcache[t * a.dcache_n + nrel]
                                       : a.desc[nb];
             if (dn.prev_doc < hi) {
-              const uint32_t* pfp = (const uint32_t*)(
-                (uintptr_t)(pl + dn.doc_off) & ~(uintptr_t)3);
+              const uint32_t* pfp = align_down4(pl + dn.doc_off);
               const uint32_t pf = pfp[lane];  // 256 B line-touch
               asm volatile("" ::"v"(pf));
             }
@@ -1323,9 +1419,8 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
                                     ? dcache[(t + 1) * a.dcache_n + wave]
                                     : a.desc[nb];
           if (dn.prev_doc < hi) {
-            const uint32_t* pfp = (const uint32_t*)(
-              (uintptr_t)(a.payload + tn.payload_begin + dn.doc_off) &
-              ~(uintptr_t)3);
+            const uint32_t* pfp =
+              align_down4(a.payload + tn.payload_begin + dn.doc_off);
             pf_next = pfp[lane] + pfp[lane + 64];  // 512 B line touch
           }
         }
@@ -1384,7 +1479,7 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
               const uint32_t tot = al + span;
               // clamp: the 16 B-aligned copy may read up to 15 B past the
               // span — only safe when another block follows in this term
-              if (tot <= SDB_STG_CAP &&
+              if (tot + SDB_FETCH_OVERREAD <= SDB_STG_CAP &&
                   te.desc_begin + cur0 + nrel + 1 < dend) {
                 const uint8_t* gsrc = (const uint8_t*)(
                   (uintptr_t)(pl + dn.doc_off) & ~(uintptr_t)15);
@@ -1455,8 +1550,7 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
                                       ? dcache[t * a.dcache_n + nrel]
                                       : a.desc[nb];
             if (dn.prev_doc < hi) {
-              const uint32_t* pfp = (const uint32_t*)(
-                (uintptr_t)(pl + dn.doc_off) & ~(uintptr_t)3);
+              const uint32_t* pfp = align_down4(pl + dn.doc_off);
               const uint32_t pf = pfp[lane];
               asm volatile("" ::"v"(pf));
             }
@@ -1564,9 +1658,8 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
       const uint32_t ncur = cursors[t];  // post-advance (barrier above)
       const uint64_t nb = te.desc_begin + ncur;
       if (nb < te.desc_end) {
-        const uint32_t* pfp = (const uint32_t*)(
-          (uintptr_t)(a.payload + te.payload_begin + a.desc[nb].doc_off) &
-          ~(uintptr_t)3);
+        const uint32_t* pfp = align_down4(a.payload + te.payload_begin +
+                                          a.desc[nb].doc_off);
         pf_w = pfp[lane] + pfp[lane + 64];
       }
     }
@@ -1846,16 +1939,10 @@ __device__ __forceinline__ uint32_t pw_fill_block(
       const uint32_t fbits = (d.flags >> 6) & 31u;
       const uint32_t nbits = (d.flags >> 11) & 31u;
       const uint8_t* nb = fb + 1 + 16u * fbits;
-      const uint32_t i0 = 2u * (uint32_t)lane, i1 = i0 + 1;
-      const uint32_t dd0 = extract_packed(db + 1, dbits, i0);
-      const uint32_t dd1 = extract_packed(db + 1, dbits, i1);
-      const uint32_t f0 = extract_packed(fb + 1, fbits, i0);
-      const uint32_t f1 = extract_packed(fb + 1, fbits, i1);
-      uint32_t n0 = 0, n1 = 0;
-      if (a.norm_stream) {
-        n0 = extract_packed(nb + 1, nbits, i0);
-        n1 = extract_packed(nb + 1, nbits, i1);
-      }
+      uint32_t dd0, dd1, f0, f1, n0 = 0, n1 = 0;
+      extract_packed_pair(db + 1, dbits, lane, &dd0, &dd1);
+      extract_packed_pair(fb + 1, fbits, lane, &f0, &f1);
+      if (a.norm_stream) extract_packed_pair(nb + 1, nbits, lane, &n0, &n1);
       const uint32_t pair = dd0 + dd1;
       const uint32_t incl = wave_incl_scan(pair, lane);
       const uint32_t excl = incl - pair;
@@ -2564,7 +2651,7 @@ int sdb_gpu_segment_load(SdbGpuCtx* ctx, const void* blob, size_t blob_size,
     }
   }
   SEG_CHECK(hipMalloc(&seg->desc, sizeof(SdbBlockDesc) * hdr.total_blocks + 16));
-  SEG_CHECK(hipMalloc(&seg->payload, hdr.payload_size + 512));
+  SEG_CHECK(hipMalloc(&seg->payload, hdr.payload_size + SDB_DEV_PAYLOAD_PAD));
   SEG_CHECK(
     hipMalloc(&seg->norms, sizeof(uint32_t) * ((size_t)hdr.doc_count + 1)));
   SEG_CHECK(hipMemcpy(seg->desc, base + hdr.off_desc,
