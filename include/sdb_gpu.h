@@ -102,6 +102,29 @@ typedef enum SdbScorerType {
   SDB_SCORER_TFIDF_NORM = 2, /* tfidf.cpp:72-76: idf*sqrt(freq)/sqrt(norm) */
 } SdbScorerType;
 
+/* The plan contract. Every entry that takes a plan (sdb_gpu_execute_topk,
+ * _batch, _count, _match_docs and the hybrid forms) checks it before anything
+ * is launched and returns SDB_ERR_INVALID otherwise; the context stays
+ * usable. Scores must be finite and >= 0: the histogram bins, the bin
+ * threshold and the WAND bounds all rest on that.
+ *   terms      non-NULL, 1..32 of them, no term twice, every term_idx below
+ *              the term count of every segment passed
+ *   boost      finite and >= 0 per term (0 is fine: the term's docs match
+ *              and count, and add nothing to a score)
+ *   scorer     a value of SdbScorerType
+ *   k1         finite and >= 0 (0 is BM1); checked whatever the scorer
+ *   b          in [0, 1] (0 is BM15); a b above 1 would make norm_const =
+ *              k1 - k1*b negative, and with it the scores
+ *   g_*        g_docs_with_field != 0 switches to the injected stats; then
+ *              g_docs_with_term is non-NULL and no entry exceeds
+ *              g_docs_with_field (0 is fine: that term scores nothing)
+ *   bound      every per-term numerator (boost * (k1 + 1) * idf, or boost *
+ *              idf) and the plan's score bound (their sum, times
+ *              sqrt(max freq) for the TFIDF forms, times the largest filter
+ *              boost) must be finite floats
+ * total_matches counts every doc matched by at least min_match terms (and
+ * live), whatever it scores: a doc scoring 0 or below the acceptance
+ * threshold is counted and never returned. */
 typedef struct SdbQueryPlan {
   const SdbTermRef* terms;
   uint32_t nterms;
@@ -129,7 +152,12 @@ typedef struct SdbQueryPlan {
   /* HasFilterBoost scorer variants (bm25.cpp:112-140 Bm1Boost, :69-109
    * Bm15/Bm25 boost[i]*num; tfidf equivalents): when nonzero, every
    * segment must have a boost column attached (sdb_gpu_segment_attach_
-   * boost) and each term contribution is multiplied by boost[doc]. With
+   * boost) and each term contribution is multiplied by boost[doc]. The
+   * boost folds into the numerator BEFORE the score form, the reference's
+   * order of operations: nm = fl(num * boost[doc]), then nm - nm*c1/(c1 +
+   * freq) or nm*sqrt(freq)[/sqrt(norm)]; multiplying the finished score
+   * instead rounds differently. A segment without a column, or columns
+   * that are 0 everywhere, are SDB_ERR_INVALID. With
    * k1 == 0 this is BM1's only nonzero form: score = boost[doc]*num.
    * (The reference's Bm1Boost ASSIGNS rather than merges under multi-term
    * disjunctions; this implementation sums term contributions uniformly —
@@ -244,8 +272,13 @@ int sdb_gpu_segment_attach_column(SdbGpuCtx* ctx, SdbGpuSegment* seg,
                                   const int64_t* data);
 int sdb_gpu_segment_attach_column_slot(SdbGpuCtx* ctx, SdbGpuSegment* seg,
                                        uint32_t slot, const int64_t* data);
-/* per-doc f32 filter-boost column (doc_count+1 entries, 1-based docs);
- * consumed when SdbQueryPlan.filter_boost is set */
+/* per-doc f32 filter-boost column (doc_count+1 entries, 1-based docs; entry
+ * 0 is not looked at); consumed when SdbQueryPlan.filter_boost is set. Every
+ * value must be finite and >= 0 (subnormals and 0 are fine): a column
+ * holding a negative value, NaN or an infinity is SDB_ERR_INVALID, nothing
+ * is uploaded and a column attached earlier stays in place. A finite
+ * maximum can still be too large for a given plan (score bound times the
+ * maximum overflows); that is refused when the plan is prepared. */
 int sdb_gpu_segment_attach_boost(SdbGpuCtx* ctx, SdbGpuSegment* seg,
                                  const float* boost);
 /* live-document bitmap — the deleted-docs mask the reference wraps around

@@ -676,8 +676,13 @@ class GpuContext:
         return res, total.value, bcnt, bsum
 
     def execute_count(self, segs, term_idx, boosts, min_match=1, k1=1.2,
-                      b=0.75):
-        plan = self._make_plan(term_idx, boosts, min_match, k1, b, None)
+                      b=0.75, global_stats=None, scorer="bm25",
+                      filter_boost=False):
+        """The scoring fields never change what matches; they are taken so
+        that a caller can count with the very plan it scores with (the
+        plan contract in sdb_gpu.h holds for this entry too)."""
+        plan = self._make_plan(term_idx, boosts, min_match, k1, b,
+                               global_stats, scorer, False, filter_boost)
         seg_arr = (C.c_void_p * len(segs))(
             *[C.c_void_p(s.value) for s in segs])
         total = C.c_uint64(0)
@@ -688,10 +693,12 @@ class GpuContext:
         return total.value
 
     def execute_match_docs(self, seg, term_idx, boosts, cap, min_match=1,
-                           k1=1.2, b=0.75, with_col=False):
+                           k1=1.2, b=0.75, with_col=False, global_stats=None,
+                           scorer="bm25", filter_boost=False):
         import numpy as np
 
-        plan = self._make_plan(term_idx, boosts, min_match, k1, b, None)
+        plan = self._make_plan(term_idx, boosts, min_match, k1, b,
+                               global_stats, scorer, False, filter_boost)
         docs = np.zeros(cap, dtype=np.uint32)
         cols = np.zeros(cap, dtype=np.int64) if with_col else None
         out_n = C.c_uint64(0)

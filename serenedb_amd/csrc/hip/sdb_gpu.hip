@@ -2710,6 +2710,14 @@ struct PlanStats {
   float nc, nl, smax, fbmax;
 };
 
+// score_bin for the host selects: the same f32 multiply and truncation, with
+// the clamp taken before the conversion (a float outside uint32's range, or
+// a NaN, converts with undefined behaviour on the host)
+static inline uint32_t sdb_host_score_bin(float s, float inv_smax) {
+  const float x = s * inv_smax;
+  return x < (float)SDB_HIST_BINS ? (uint32_t)x : SDB_HIST_BINS - 1;
+}
+
 // PreparePhase analogue: global stats (double -> f32, bm25.cpp:288-306);
 // shared by the single-query and the pipelined batch executors.
 static int prep_plan_stats(SdbGpuSegment* const* segs, uint32_t nsegs,
@@ -2720,6 +2728,30 @@ static int prep_plan_stats(SdbGpuSegment* const* segs, uint32_t nsegs,
                            const SdbQueryPlan* plan, int hybrid,
                            PlanStats* out) {
   (void)hybrid;
+  // The plan contract (sdb_gpu.h, SdbQueryPlan), checked before anything is
+  // launched. Everything downstream (histogram bins, bin-threshold
+  // monotonicity, WAND bounds, the host select) assumes finite scores >= 0:
+  // b > 1 makes nc = k1 - k1*b negative, so c1 + freq can reach 0 or below;
+  // a negative or NaN k1 does the same; an unknown scorer would take the
+  // TFIDF num into the BM25 form.
+  if (!segs || !plan->terms || plan->scorer > SDB_SCORER_TFIDF_NORM)
+    return SDB_ERR_INVALID;
+  if (!(plan->k1 >= 0.0f && plan->k1 <= FLT_MAX)) return SDB_ERR_INVALID;
+  if (!(plan->b >= 0.0f && plan->b <= 1.0f)) return SDB_ERR_INVALID;
+  for (uint32_t t = 0; t < plan->nterms; ++t) {
+    if (!(plan->terms[t].boost >= 0.0f && plan->terms[t].boost <= FLT_MAX))
+      return SDB_ERR_INVALID;
+    for (uint32_t s = 0; s < nsegs; ++s)
+      if (plan->terms[t].term_idx >= segs[s]->hdr.nterms)
+        return SDB_ERR_INVALID;
+  }
+  if (plan->g_docs_with_field) {
+    // idf takes g_dwf - g_dwt[t] as an unsigned difference
+    if (!plan->g_docs_with_term) return SDB_ERR_INVALID;
+    for (uint32_t t = 0; t < plan->nterms; ++t)
+      if (plan->g_docs_with_term[t] > plan->g_docs_with_field)
+        return SDB_ERR_INVALID;
+  }
   float fbmax = 1.0f;  // filter boost: every segment needs the column
   if (plan->filter_boost) {
     fbmax = 0.0f;
@@ -2779,6 +2811,8 @@ static int prep_plan_stats(SdbGpuSegment* const* segs, uint32_t nsegs,
       const float ub = out->num[t] * sqrtf((float)term_max_freq);
       smax += ub > 0 ? ub : 0.0f;
     }
+    // a large finite boost overflows num: every score would be inf - inf
+    if (!(out->num[t] <= FLT_MAX)) return SDB_ERR_INVALID;
   }
   if (scorer == SDB_SCORER_BM25) {
     const float kb = k1 * b;
@@ -2791,6 +2825,8 @@ static int prep_plan_stats(SdbGpuSegment* const* segs, uint32_t nsegs,
     }
   }
   if (plan->filter_boost) smax *= fbmax;  // scores reach fb*base
+  // the score bound itself must be finite (inv_smax would be 0)
+  if (!(smax <= FLT_MAX)) return SDB_ERR_INVALID;
   // smax <= 0: all scores are 0; 1.0 keeps inv_smax finite (bin 0)
   if (smax <= 0.0f) smax = 1.0f;
   out->nc = nc;
@@ -2808,8 +2844,9 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
                           int64_t* bucket_count, int64_t* bucket_sum,
                           SdbScoreDoc* hits, uint32_t* out_count,
                           uint64_t* total_matches, int count_only = 0) {
-  if (!ctx || !segs || !plan || !out_count || !total_matches ||
-      plan->nterms == 0 || plan->nterms > SDB_MAX_TERMS || k == 0)
+  if (!ctx || !segs || !plan || !plan->terms || !out_count ||
+      !total_matches || plan->nterms == 0 ||
+      plan->nterms > SDB_MAX_TERMS || k == 0)
     return SDB_ERR_INVALID;
   /* hits == NULL: candidate-only mode (streaming match emission reads the
    * device candidate buffer itself; no host select) */
@@ -3106,9 +3143,8 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
   size_t n = 0;
   for (size_t i = 0; i < ncand; ++i) {
     const float s = cands[i].score;
-    uint32_t sb = (uint32_t)(s * inv_smax);
-    if (sb >= SDB_HIST_BINS) sb = SDB_HIST_BINS - 1;
-    if (sb >= final_bin && s > FLT_MIN) cands[n++] = cands[i];
+    if (sdb_host_score_bin(s, inv_smax) >= final_bin && s > FLT_MIN)
+      cands[n++] = cands[i];
   }
   const float gtau_final =
     final_bin ? (float)final_bin / inv_smax : 0.0f;  // diagnostic only
@@ -3175,9 +3211,9 @@ static int exec_topk_batch_impl(
   const SdbHybridPred* hpreds, uint32_t nhp, uint32_t h_nbuckets,
   int64_t* bucket_counts, int64_t* bucket_sums, SdbScoreDoc* hits,
   uint32_t* out_counts, uint64_t* totals) {
-  if (!ctx || !segs || !plan || !hits || !out_counts || !totals ||
-      nq == 0 || plan->nterms == 0 || plan->nterms > SDB_MAX_TERMS ||
-      k == 0 || k == 0xFFFFFFFFu)
+  if (!ctx || !segs || !plan || !plan->terms || !hits || !out_counts ||
+      !totals || nq == 0 || plan->nterms == 0 ||
+      plan->nterms > SDB_MAX_TERMS || k == 0 || k == 0xFFFFFFFFu)
     return SDB_ERR_INVALID;
   const bool hybrid = nhp > 0;
   if (hybrid) {  // same contract as exec_topk_impl's hybrid arm
@@ -3439,9 +3475,8 @@ static int exec_topk_batch_impl(
     size_t n = 0;
     for (size_t i = 0; i < ncand; ++i) {
       const float sc = cands[i].score;
-      uint32_t sb = (uint32_t)(sc * inv_smax);
-      if (sb >= SDB_HIST_BINS) sb = SDB_HIST_BINS - 1;
-      if (sb >= final_bin && sc > FLT_MIN) cands[n++] = cands[i];
+      if (sdb_host_score_bin(sc, inv_smax) >= final_bin && sc > FLT_MIN)
+        cands[n++] = cands[i];
     }
     auto cmp = [](const SdbScoreDoc& x, const SdbScoreDoc& y) {
       if (x.score != y.score) return x.score > y.score;
@@ -3518,7 +3553,7 @@ int sdb_gpu_execute_topk_hybrid_batch(
 int sdb_gpu_execute_count(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
                           uint32_t nsegs, const SdbQueryPlan* plan,
                           uint64_t* total_matches) {
-  if (!total_matches) return SDB_ERR_INVALID;
+  if (!total_matches || !plan) return SDB_ERR_INVALID;
   SdbQueryPlan p = *plan;
   p.wand = 0;
   uint32_t n = 0;
@@ -3554,10 +3589,11 @@ int sdb_gpu_segment_attach_boost(SdbGpuCtx* ctx, SdbGpuSegment* seg,
   if (!ctx || !seg || !boost) return SDB_ERR_INVALID;
   const uint64_t n = (uint64_t)seg->hdr.doc_count + 1;
   // negative/NaN boosts break the non-negative-score machinery (histogram
-  // bins, bin-threshold monotonicity, WAND bounds) — reject before upload
+  // bins, bin-threshold monotonicity, WAND bounds) — reject before upload;
+  // +inf likewise (inf * 0 scores, an infinite score bound)
   float mx = 0.0f;
   for (uint64_t i = 1; i < n; ++i) {
-    if (!(boost[i] >= 0.0f)) return SDB_ERR_INVALID;
+    if (!(boost[i] >= 0.0f && boost[i] <= FLT_MAX)) return SDB_ERR_INVALID;
     mx = boost[i] > mx ? boost[i] : mx;
   }
   if (!seg->fboost) HIP_CHECK(hipMalloc(&seg->fboost, 4ull * n));

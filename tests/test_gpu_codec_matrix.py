@@ -82,7 +82,7 @@ def test_decode_term(ctx, seg, m):
         np.testing.assert_array_equal(dfreqs, freqs, err_msg=m.names[t])
 
 
-@pytest.mark.parametrize("scorer", GPU_SCORERS)
+@pytest.mark.parametrize("scorer", GPU_SCORERS + ("tfidf",))
 def test_sweep_single_terms(ctx, seg, m, scorer):
     """default path, every term alone with k = df + 1: the hits are the
     complete decoded posting list with its scores, total == df"""
