@@ -439,19 +439,60 @@ __device__ __forceinline__ void mark_match_mask(void* cnt, uint32_t off) {
   atomicOr((unsigned long long*)cnt + (off >> 6), 1ull << (off & 63u));
 }
 
-// swin accumulate: each doc gets exactly ONE add per term phase (docs are
-// unique within a term) and phases are barrier-ordered, so the add sequence
-// per slot is deterministic either way. SDB_DSADD uses the no-return LDS
-// float atomic (ds_add_f32): no ds_read -> wait -> add -> write chain per
-// posting. Bit-exactness vs the VALU add is gated by the parity suite.
+// swin accumulate: each doc gets exactly ONE add per term (docs are unique
+// within a term) and terms are barrier-ordered, so the add sequence per slot
+// is deterministic.
 __device__ __forceinline__ void swin_add(float* swin, uint32_t off,
                                          float s) {
-#ifdef SDB_DSADD
-  (void)atomicAdd(&swin[off], s);
-#else
   swin[off] += s;
-#endif
 }
+
+// Where a decoded posting goes. The decode bodies below hand every posting
+// of a block to a sink: put(e, off, s) for one inside the window, skip(e)
+// for one outside it, then flush(blk, lane) once per block. e counts the
+// lane's values (0,1 = first block, 2,3 = second block of a fused pair).
+//
+// WindowSink adds straight into the score window and bumps the u8 match
+// count (the general window kernel).
+struct WindowSink {
+  float* swin;
+  void* cwin;
+  __device__ __forceinline__ void put(int, uint32_t off, float s) {
+    swin_add(swin, off, s);
+    mark_match_u8(cwin, off);
+  }
+  __device__ __forceinline__ void skip(int) {}
+  __device__ __forceinline__ void flush(int, int) {}
+};
+
+// SlotSink (sweep kernel, stage 1) writes (window offset, score) into the
+// block's 128-entry slot of the LDS posting stage instead: 128 f32 scores,
+// then 128 u16 offsets, SDB_SLOT_ABSENT for a posting outside the window.
+// A lane owns two adjacent entries, so a block costs it one 8-byte and one
+// 4-byte store. The match bit is order-free and is set here.
+#define SDB_SLOT_BYTES 768u
+#define SDB_SLOT_ABSENT 0xFFFFu
+struct SlotSink {
+  char* slot[2];
+  void* mwin;
+  float s[4];
+  uint32_t o[4];
+  __device__ __forceinline__ void put(int e, uint32_t off, float sv) {
+    s[e] = sv;
+    o[e] = off;
+    mark_match_mask(mwin, off);
+  }
+  __device__ __forceinline__ void skip(int e) {
+    s[e] = 0.0f;
+    o[e] = SDB_SLOT_ABSENT;
+  }
+  __device__ __forceinline__ void flush(int blk, int lane) {
+    float2 v;
+    v.x = s[2 * blk], v.y = s[2 * blk + 1];
+    ((float2*)slot[blk])[lane] = v;
+    ((uint32_t*)(slot[blk] + 512))[lane] = o[2 * blk] | (o[2 * blk + 1] << 16);
+  }
+};
 
 // Fused fast path for the dominant block shape (delta-bitpack docs +
 // bitpack freqs + bitpack norms, always full 128-doc blocks): issue every
@@ -459,26 +500,12 @@ __device__ __forceinline__ void swin_add(float* swin, uint32_t off,
 // three serialized ones), keep the two values per lane in registers, score
 // directly — no LDS scratch round trip. Returns false for any other family
 // combination (caller falls back to the generic per-stream decode).
-#ifdef SDB_SWEEP_STAGE
-// LDS-DMA payload staging (sweep kernel): per (wave, term<=4) slot holding
-// one fused block's raw payload bytes, filled with global_load_lds_dwordx4
-// during the PREVIOUS window's phases so next window's first-block decode
-// reads LDS instead of riding an exposed HBM round trip.
-#define SDB_STG_TERMS 4
-// 22 x 16 B. A block is staged only when align pad + fused span
-// 3+16*(db+fb+nb) + SDB_FETCH_OVERREAD fits, so the decode's over-read
-// stays inside the slot (its bytes past the span are stale and masked off)
-#define SDB_STG_CAP 352
-#endif
-
-template <int LEAN>
+template <class Sink>
 __device__ __forceinline__ bool try_block_fused(
-  const uint8_t* db0 /* doc-block base: global payload or an LDS-staged
-                        copy (the three streams are contiguous) */,
+  const uint8_t* db0 /* doc-block base (the three streams are contiguous) */,
   const SdbBlockDesc& d, int lane, uint32_t norm_stream, uint32_t lo,
   uint32_t hi, float num, float nc, float nl, uint32_t scorer,
-  const uint32_t* norms_col, const float* fboost, float* swin,
-  void* cwin) {
+  const uint32_t* norms_col, const float* fboost, Sink& sink) {
   // v3 descriptors carry the fused-shape bit + all three bit widths, so
   // every packed-word load below issues with NO payload-tag fetch first
   // (one whole memory round trip per block saved; sdb_format.h flags)
@@ -511,40 +538,43 @@ __device__ __forceinline__ bool try_block_fused(
   if (doc0 >= lo && doc0 <= hi) {
     const float nm = fboost ? num * fboost[doc0] : num;
     const float s = score_one(scorer, nm, nc, nl, f0, n0);
-    const uint32_t off = doc0 - lo;
-    swin_add(swin, off, s);
-    if (LEAN) mark_match_mask(cwin, off); else mark_match_u8(cwin, off);
+    sink.put(0, doc0 - lo, s);
+  } else {
+    sink.skip(0);
   }
   if (doc1 >= lo && doc1 <= hi) {
     const float nm = fboost ? num * fboost[doc1] : num;
     const float s = score_one(scorer, nm, nc, nl, f1, n1);
-    const uint32_t off = doc1 - lo;
-    swin_add(swin, off, s);
-    if (LEAN) mark_match_mask(cwin, off); else mark_match_u8(cwin, off);
+    sink.put(1, doc1 - lo, s);
+  } else {
+    sink.skip(1);
   }
+  sink.flush(0, lane);
   return true;
 }
 
 // Dual-block fused path: both blocks' packed-word loads are issued before
 // either scan, so the two dependent-load chains overlap (the decode phase
 // is latency-bound — SDB_TIMING showed it at 43% of the kernel).
-template <int LEAN>
+// The two blocks may belong to different terms (sweep kernel): each has its
+// own payload base and num; nc and nl are plan-wide.
+template <class Sink>
 __device__ __forceinline__ bool try_block_fused2(
-  const uint8_t* pl, const SdbBlockDesc& da, const SdbBlockDesc& db_,
-  int lane, uint32_t norm_stream, uint32_t lo, uint32_t hi, float num,
-  float nc, float nl, uint32_t scorer, const uint32_t* norms_col,
-  const float* fboost, float* swin, void* cwin) {
+  const uint8_t* pla, const uint8_t* plb, const SdbBlockDesc& da,
+  const SdbBlockDesc& db_, int lane, uint32_t norm_stream, uint32_t lo,
+  uint32_t hi, float numa, float numb, float nc, float nl, uint32_t scorer,
+  const uint32_t* norms_col, const float* fboost, Sink& sink) {
   if (!(da.flags & 1u) || !(db_.flags & 1u) || !norm_stream)
     return false;  // widths come from the descriptors (sdb_format.h)
   const uint32_t adb = (da.flags >> 1) & 31u, afb = (da.flags >> 6) & 31u;
   const uint32_t anb = (da.flags >> 11) & 31u;
   const uint32_t bdb = (db_.flags >> 1) & 31u, bfb = (db_.flags >> 6) & 31u;
   const uint32_t bnb = (db_.flags >> 11) & 31u;
-  const uint8_t* adoc = pl + da.doc_off;
-  const uint8_t* afrq = pl + da.freq_off;
+  const uint8_t* adoc = pla + da.doc_off;
+  const uint8_t* afrq = pla + da.freq_off;
   const uint8_t* anrm = afrq + 1 + 16u * afb;
-  const uint8_t* bdoc = pl + db_.doc_off;
-  const uint8_t* bfrq = pl + db_.freq_off;
+  const uint8_t* bdoc = plb + db_.doc_off;
+  const uint8_t* bfrq = plb + db_.freq_off;
   const uint8_t* bnrm = bfrq + 1 + 16u * bfb;
   // twelve 12-byte loads, no tag fetch before them and none depending on
   // another's data: all issue before the first wait
@@ -579,13 +609,17 @@ __device__ __forceinline__ bool try_block_fused2(
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const uint32_t doc = docs[e];
-    if (doc < lo || doc > hi) continue;
+    if (doc < lo || doc > hi) {
+      sink.skip(e);
+      continue;
+    }
+    const float num = e < 2 ? numa : numb;
     const float nm = fboost ? num * fboost[doc] : num;  // reference op order
     const float s = score_one(scorer, nm, nc, nl, frqs[e], nrms[e]);
-    const uint32_t off = doc - lo;
-    swin_add(swin, off, s);
-    if (LEAN) mark_match_mask(cwin, off); else mark_match_u8(cwin, off);
+    sink.put(e, doc - lo, s);
   }
+  sink.flush(0, lane);
+  sink.flush(1, lane);
   return true;
 }
 
@@ -653,6 +687,8 @@ struct WindowArgs {
   unsigned long long* bucket_out;  // [2*nbuckets]: count, sum (i64 bits)
   uint32_t dcache_n;  // staged descriptors per term (host-shrunk so the
                       // cache fits LDS for wide plans; <= SDB_DESC_CACHE)
+  uint32_t round_items;  // sweep kernel: slots of the LDS posting stage
+                         // (plan_sweep_lds; >= one per wave)
   const unsigned long long* live;  // live-doc bitmap or null (all live);
                                    // applied BEFORE match counts,
                                    // histogram and appends (a masked doc
@@ -695,6 +731,7 @@ void topk_window_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
   const int lane = tid & 63;
   const uint32_t wave = tid >> 6;
   const uint32_t mm = a.min_match ? a.min_match : 1u;
+  WindowSink wsink{swin, cwin};
   const float inv_smax = (float)SDB_HIST_BINS / a.smax;
   uint32_t* gh = a.ghist + (blockIdx.x & 7u) * SDB_HIST_BINS;
 
@@ -879,9 +916,9 @@ void topk_window_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
                                       ? dcache[t * a.dcache_n + rel2]
                                       : a.desc[b2];
             if (d2.prev_doc < hi && d.len == 128 && d2.len == 128 &&
-                try_block_fused2<0>(pl, d, d2, lane, a.norm_stream, lo,
-                                    hi, num, nc, nl, a.scorer, a.norms,
-                                    a.fb, swin, cwin)) {
+                try_block_fused2(pl, pl, d, d2, lane, a.norm_stream, lo,
+                                 hi, num, num, nc, nl, a.scorer, a.norms,
+                                 a.fb, wsink)) {
               b += 2 * SDB_NWAVES;
               continue;
             }
@@ -913,9 +950,9 @@ void topk_window_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
         }
 #else
 #ifndef SDB_ABLATE_SCORE
-        if (try_block_fused<0>(pl + d.doc_off, d, lane, a.norm_stream, lo,
-                               hi, num, nc, nl, a.scorer, a.norms, a.fb,
-                               swin, cwin)) {
+        if (try_block_fused(pl + d.doc_off, d, lane, a.norm_stream, lo,
+                            hi, num, nc, nl, a.scorer, a.norms, a.fb,
+                            wsink)) {
           b += SDB_NWAVES;  // while-loop: explicit advance before continue
           continue;
         }
@@ -1196,8 +1233,8 @@ void topk_window_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
 
 // ---------------------------------------------------------------------------
 // Lean sweep kernel (round-2): the headline path (min_match == 1, no pushed
-// column filter, scored). Same term-major phase structure and bit-exact
-// fp32 merge order as topk_window_kernel, but reshaped for throughput
+// column filter, scored). Same term-major, bit-exact fp32 merge order as
+// topk_window_kernel, but reshaped for throughput
 // (round-1 VERDICT: 1.1% of the HBM roofline, latency/overhead-bound):
 //  - the u8 match-count window becomes a u64 match BITMASK (min_match==1
 //    only needs membership): zeroing drops 16x, the match count is a
@@ -1210,18 +1247,37 @@ void topk_window_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
 //    windows at 2 workgroups/CU let one WG's decode cover the other's
 //    term barriers (the fixed 24576x1024 1-WG/CU shape left every barrier
 //    stall empty).
+//
+// Per window the postings go through two stages ("Round stage"):
+//  1. every block of every term that intersects the window is an ITEM,
+//     numbered term-major. Items are dealt over all NW waves, which decode
+//     and score them with no barrier in between and write each posting's
+//     (window offset, score) into the item's slot of an LDS posting stage;
+//  2. after one barrier the slots are merged into swin term by term, all
+//     threads striding over one term's entries, one barrier between terms.
+// Only the add order per doc must be term-major; decode, scoring and the
+// memory wait need none. The stage holds a.round_items slots: a window with
+// more items runs in rounds of that many, in item order, each round merged
+// before the next is decoded, so the per-doc order holds for any plan.
+struct SweepItem {
+  uint32_t t;         // term
+  float num;          // the term's num
+  const uint8_t* pl;  // the term's payload base
+  SdbBlockDesc d;
+};
+
 template <uint32_t WD, uint32_t NTH, bool WIDE>
 // WIDE as in topk_window_kernel.
 // 2nd launch-bounds arg = min waves/SIMD. A 1024-thread WG forces 4/SIMD
-// (VGPRs <= 128), and at that cap the kernel spills ~65 SGPRs to SCRATCH
-// (212 B/thread private segment measured via rocprofv3) — reloads in the
-// window loop. 512-thread WGs declare 2/SIMD instead: 256 VGPRs, no
-// scratch, trading TLP for a clean register file.
+// (VGPRs <= 128); 512-thread WGs declare 2/SIMD instead: 256 VGPRs,
+// trading TLP for a clean register file.
 __launch_bounds__(NTH, NTH == 1024 ? 4 : 2) __global__
 void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
   constexpr uint32_t NW = NTH / 64u;
   constexpr uint32_t NWORDS = WD / 64u;
+  static_assert(WD - 1u < SDB_SLOT_ABSENT, "slot offsets are u16");
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  // layout mirrored by sweep_lds_fixed() on the host
   float* swin = (float*)smem;                                   // WD * 4
   unsigned long long* mwin = (unsigned long long*)(swin + WD);  // NWORDS * 8
   uint32_t* scratch = (uint32_t*)(mwin + NWORDS);               // NW * 384
@@ -1229,27 +1285,24 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
   uint32_t* shared_misc = hist + SDB_HIST_BINS;                 // 2 + NW
   uint32_t* cursors = shared_misc + 2 + NW;                     // max terms
   float* wub = (float*)(cursors + SDB_MAX_TERMS);               // max terms
-  TermDev* tstage = (TermDev*)(wub + SDB_MAX_TERMS);            // max terms
+  uint32_t* icnt = (uint32_t*)(wub + SDB_MAX_TERMS);  // items per term
+  uint32_t* iadv = icnt + SDB_MAX_TERMS;  // cursor advance per term
+  TermDev* tstage = (TermDev*)(iadv + SDB_MAX_TERMS);           // nterms
   unsigned long long* lbuck =
-    (unsigned long long*)(tstage + SDB_MAX_TERMS);  // 2 * max buckets
-  SdbBlockDesc* dcache = (SdbBlockDesc*)(lbuck + 2 * SDB_MAX_BUCKETS);
-#ifdef SDB_SWEEP_STAGE
-  // slot metadata: (align<<28)|block-index-within-term, ~0u = empty; the
-  // slot content is ALWAYS the payload of exactly the block the index
-  // names, so a stale entry that still matches the cursor is a valid hit
-  uint32_t* smeta = (uint32_t*)&dcache[a.nterms * a.dcache_n];
-  uint8_t* stg = (uint8_t*)(((uintptr_t)(smeta + NW * SDB_STG_TERMS) + 15) &
-                            ~(uintptr_t)15);
-#endif
+    (unsigned long long*)(tstage + a.nterms);  // 2 * max buckets, hybrid only
+  SdbBlockDesc* dcache =
+    (SdbBlockDesc*)(lbuck + (a.fcol ? 2 * SDB_MAX_BUCKETS : 0u));
+  // posting stage: a.round_items slots of SDB_SLOT_BYTES, 16 B aligned
+  const uint32_t stage_off =
+    ((uint32_t)((char*)(dcache + a.nterms * a.dcache_n) - smem) + 15u) & ~15u;
+  char* stage = smem + stage_off;
+  const uint32_t C = a.round_items;
 
   const uint32_t tid = threadIdx.x;
   const int lane = tid & 63;
   const uint32_t wave = tid >> 6;
-#ifdef SDB_SWEEP_STAGE
-  if (tid < NW * SDB_STG_TERMS) smeta[tid] = ~0u;
-#endif
-  // stage the term table through the vector path once: per-phase reads
-  // of the global term table are wave-uniform SMEM loads whose lgkmcnt
+  // stage the term table through the vector path once: per-item reads of
+  // the global term table are wave-uniform SMEM loads whose lgkmcnt
   // sharing with LDS ops stalls every later LDS wait (see load_tags3)
   for (uint32_t i = tid; i < a.nterms * (sizeof(TermDev) / 4); i += NTH)
     ((uint32_t*)tstage)[i] = ((const uint32_t*)terms)[i];
@@ -1257,6 +1310,7 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
   uint32_t* gh = a.ghist + (blockIdx.x & 7u) * SDB_HIST_BINS;
   unsigned long long wg_matches = 0;
 #ifdef SDB_TIMING
+  // slots: 0 zero+stage, 1 stage 1, 2 stage 2, 3 sweep, 4 tau, 5 append
   unsigned long long t_acc[6] = {0, 0, 0, 0, 0, 0};
   long long t_mark = clock64();
 #define SDB_TS(idx)                                        \
@@ -1286,6 +1340,7 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
       te.desc_begin);
   }
   __syncthreads();
+  const float nc = tstage[0].nc, nl = tstage[0].nl;  // plan-wide
 
   for (uint32_t w = w_lo; w < w_hi; ++w) {
     const uint32_t lo = 1u + w * WD;
@@ -1295,16 +1350,35 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
     const bool derive = ((w & 3u) == 0) || (w < w_lo + 2);
     uint32_t my_excl_snap = 0;
 
-#ifdef SDB_MACH
-    // b128 zero stores: same LDS bandwidth, 4x fewer ops + iterations
-    {
-      float4 z4;
-      z4.x = z4.y = z4.z = z4.w = 0.0f;
-      for (uint32_t i = tid; i < WD / 4; i += NTH) ((float4*)swin)[i] = z4;
+    // count this window's items, wave-parallel from the global descriptors
+    // (no wait on the staging below): term t contributes the blocks from
+    // its cursor whose prev_doc < hi (icnt); those of them whose last_doc
+    // <= hi are done after this window (iadv). Both sets are prefixes of
+    // the term's block list, so a ballot per 64 blocks counts them; a dense
+    // term takes several.
+    for (uint32_t t = wave; t < a.nterms; t += NW) {
+      const TermDev te = tstage[t];
+      uint64_t b = te.desc_begin + cursors[t] + (uint32_t)lane;
+      uint32_t cnt = 0, adv = 0;
+      for (;;) {
+        uint32_t prev = 0xFFFFFFFFu, last = 0xFFFFFFFFu;
+        if (b < te.desc_end) {
+          prev = a.desc[b].prev_doc;
+          last = a.desc[b].last_doc;
+        }
+        const uint32_t c = (uint32_t)__popcll(__ballot(prev < hi));
+        adv += (uint32_t)__popcll(__ballot(last <= hi));
+        cnt += c;
+        if (c < 64u) break;
+        b += 64u;
+      }
+      if (lane == 0) {
+        icnt[t] = cnt;
+        iadv[t] = adv;
+      }
     }
-#else
+
     for (uint32_t i = tid; i < WD; i += NTH) swin[i] = 0.0f;
-#endif
     for (uint32_t i = tid; i < NWORDS; i += NTH) mwin[i] = 0ull;
     if (derive)
       for (uint32_t i = tid; i < SDB_HIST_BINS; i += NTH) hist[i] = 0;
@@ -1326,10 +1400,6 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
             ((const uint32_t*)&a.desc[b0])[wrd];
       }
     }
-    // (a window-start cross-term payload prefetch was tried here and
-    // REVERTED: +5% kernel time at 1B — the 7-lane desc read + shuffle
-    // chain and the extra VMEM pressure cost more than the overlap won;
-    // gpurun_out/r2_pf_1b.log)
     if (tid == 0)
       shared_misc[0] = __hip_atomic_load(a.gthresh, __ATOMIC_RELAXED,
                                          __HIP_MEMORY_SCOPE_AGENT);
@@ -1337,9 +1407,7 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
     if (a.wand) {
       // per-term window score upper bounds, WAVE-parallel: lane l reads
       // staged desc l of the wave's term and the bound max-reduces via
-      // shuffles (the round-1 serial per-thread walk left 1020 of 1024
-      // threads idle for ~1.6k cycles per window — the measured reason
-      // exact WAND pruning lost time even at 18% visits)
+      // shuffles
       for (uint32_t t = wave; t < a.nterms; t += NW) {
         const TermDev te = tstage[t];
         const uint32_t cur0w = cursors[t];
@@ -1374,11 +1442,6 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
       }
     }
     __syncthreads();
-#ifdef SDB_SWEEP_STAGE
-    // the previous window's global_load_lds writes must be visible before
-    // any staged-slot read below (normally already drained at a barrier)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     SDB_TS(0)
     float wand_total_ub = 0.0f;
     if (a.wand)
@@ -1392,277 +1455,174 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
       __builtin_memcpy(&gtw, &t0b, 4);
     }
 
-    // term-major phases (fixed fp32 merge order -> bit-exact vs oracle).
-    // Cross-phase prefetch: before working term t, issue a non-blocking
-    // touch of term t+1's first block payload for this wave; the value is
-    // consumed at the END of the phase, so the next phase's cold HBM/L3
-    // miss overlaps this phase's work and barrier (phases measured
-    // latency-bound: 62% of the kernel, SDB_TIMING r2).
-    uint32_t pf_acc = 0;
-    for (uint32_t t = 0; t < a.nterms; ++t) {
+    // item numbering: lane t of every wave holds term t's item range
+    // [ipre_incl - icnt, ipre_incl); item -> term is one ballot
+    const uint32_t icnt_l = (uint32_t)lane < a.nterms ? icnt[lane] : 0u;
+    const uint32_t ipre_incl = wave_incl_scan(icnt_l, lane);
+    const uint32_t ipre_excl = ipre_incl - icnt_l;
+    const uint32_t nitems =
+      (uint32_t)__builtin_amdgcn_readlane((int)ipre_incl, 63);
+    // descriptors come through two typed branches (an LDS read or a global
+    // read), never through a pointer select: that compiles to a generic
+    // load behind a full vmcnt(0) lgkmcnt(0) drain
+    auto load_item = [&](uint32_t i, SweepItem& it) {
+      const uint32_t t =
+        (uint32_t)__builtin_ctzll(__ballot(ipre_incl > i));  // i < nitems
+      const uint32_t rel =
+        i - (uint32_t)__builtin_amdgcn_readlane((int)ipre_excl, (int)t);
       const TermDev te = tstage[t];
-      const uint8_t* pl = a.payload + te.payload_begin;
-      const uint64_t dend = te.desc_end;
-      uint32_t* dbuf = scratch + wave * 384;
-      uint32_t* fbuf = dbuf + 128;
-      uint32_t* nbuf = fbuf + 128;
-      const float num = te.num, nc = te.nc, nl = te.nl;
-      const uint32_t cur0 = cursors[t];
-      uint64_t b = te.desc_begin + cur0 + wave;
-      uint32_t pf_next = 0;
-      if (t + 1 < a.nterms) {
-        const TermDev tn = tstage[t + 1];
-        const uint32_t ncur = cursors[t + 1];
-        const uint64_t nb = tn.desc_begin + ncur + wave;
-        if (nb < tn.desc_end) {
-          const SdbBlockDesc dn = wave < a.dcache_n
-                                    ? dcache[(t + 1) * a.dcache_n + wave]
-                                    : a.desc[nb];
-          if (dn.prev_doc < hi) {
-            const uint32_t* pfp =
-              align_down4(a.payload + tn.payload_begin + dn.doc_off);
-            pf_next = pfp[lane] + pfp[lane + 64];  // 512 B line touch
-          }
-        }
-      }
-      while (b < dend) {
-        const uint32_t rel = (uint32_t)(b - te.desc_begin) - cur0;
-        const SdbBlockDesc d = rel < a.dcache_n
-                                 ? dcache[t * a.dcache_n + rel]
-                                 : a.desc[b];
-        if (d.prev_doc >= hi) break;
-        if (a.wand) {
-          const float own =
-            score_one(a.scorer, num, nc, nl, d.max_freq, d.min_norm) *
-            a.fbmax * 1.0000019f;
-          if (own + (wand_total_ub - wub[t]) < gtw) {
-            b += NW;
-            continue;
-          }
-        }
-#ifdef SDB_SWEEP_STAGE
-        bool stg_hit = false;
-        if (rel == wave && t < SDB_STG_TERMS) {
-          // this wave's FIRST block of the phase: consume the staged copy
-          // if the slot holds exactly this block, then re-arm the slot
-          // with next window's first block (slot is wave-private)
-          uint32_t* mslot = &smeta[wave * SDB_STG_TERMS + t];
-          const uint32_t mv = *mslot;
-          if (((mv ^ (cur0 + wave)) & 0x0FFFFFFFu) == 0 && mv != ~0u) {
-            const uint8_t* db0 =
-              stg + (wave * SDB_STG_TERMS + t) * SDB_STG_CAP + (mv >> 28);
-            if (try_block_fused<1>(db0, d, lane, a.norm_stream, lo, hi,
-                                   num, nc, nl, a.scorer, a.norms, a.fb,
-                                   swin, mwin))
-              stg_hit = true;
-          }
-          // re-stage: predict this term's post-window cursor from the
-          // staged last_docs (wave-parallel ballot), pick next first block
-          uint32_t nmeta = ~0u;
-          const uint64_t rem64 = dend - (te.desc_begin + cur0);
-          const uint32_t avail =
-            rem64 < a.dcache_n ? (uint32_t)rem64 : a.dcache_n;
-          uint32_t lastd = 0xFFFFFFFFu;
-          if ((uint32_t)lane < avail)
-            lastd = dcache[t * a.dcache_n + lane].last_doc;
-          const unsigned long long inwin = __ballot(lastd <= hi);
-          const uint32_t adv = (uint32_t)__builtin_ctzll(~inwin);
-          const uint32_t nrel = adv + wave;
-          if (adv < avail && nrel < avail) {
-            const SdbBlockDesc dn = dcache[t * a.dcache_n + nrel];
-            if (dn.flags & 1u) {
-              const uint32_t fbits = (dn.flags >> 6) & 31u;
-              const uint32_t nbits = (dn.flags >> 11) & 31u;
-              const uint32_t span = (uint32_t)(dn.freq_off - dn.doc_off) +
-                                    2u + 16u * (fbits + nbits);
-              const uint32_t al = (uint32_t)(dn.doc_off & 15u);
-              const uint32_t tot = al + span;
-              // clamp: the 16 B-aligned copy may read up to 15 B past the
-              // span — only safe when another block follows in this term
-              if (tot + SDB_FETCH_OVERREAD <= SDB_STG_CAP &&
-                  te.desc_begin + cur0 + nrel + 1 < dend) {
-                const uint8_t* gsrc = (const uint8_t*)(
-                  (uintptr_t)(pl + dn.doc_off) & ~(uintptr_t)15);
-                uint8_t* ldst =
-                  stg + (wave * SDB_STG_TERMS + t) * SDB_STG_CAP;
-                const uint32_t nv = (tot + 15u) >> 4;
-                if ((uint32_t)lane < nv)
-                  __builtin_amdgcn_global_load_lds(
-                    (const uint32_t*)(gsrc + 16 * lane), (uint32_t*)ldst,
-                    16, 0, 0);
-                nmeta = (al << 28) | ((cur0 + nrel) & 0x0FFFFFFFu);
-              }
-            }
-          }
-          if (lane == 0) *mslot = nmeta;
-          if (stg_hit) {
-            b += NW;
-            continue;
-          }
-        }
-#endif
-#ifdef SDB_ABLATE_NOLOAD
-        // perf ablation: fabricate postings with NO payload access at all
-        // (no fused pair, no prefetch; results are WRONG)
-        {
-          const uint32_t span = d.last_doc - d.prev_doc;
-          const uint32_t i0 = 2u * (uint32_t)lane;
+      // address-space-typed pointers: as plain pointers the two branches'
+      // loads are merged back into one generic load behind a pointer phi
+      typedef __attribute__((address_space(3))) const uint32_t LdsWord;
+      typedef __attribute__((address_space(1))) const uint32_t GlobalWord;
+      uint32_t wv[10];
+      if (rel < a.dcache_n) {
+        LdsWord* p = (LdsWord*)&dcache[t * a.dcache_n + rel];
 #pragma unroll
-          for (uint32_t e = 0; e < 2; ++e) {
-            const uint32_t i = i0 + e;
-            if (i >= d.len) break;
-            const uint32_t doc =
-              d.prev_doc + 1 + (uint32_t)(((uint64_t)i * span) / 128u);
-            if (doc < lo || doc > hi) continue;
-            const float sc = score_one(a.scorer, num, nc, nl, 1 + (i & 7),
-                                       100 + i);
-            const uint32_t off = doc - lo;
-            swin[off] += sc;
-            mark_match_mask(mwin, off);
-          }
-        }
-        b += NW;
-        continue;
-#endif
-        // pair with the wave's next block when both are the fused shape
-        {
-          const uint64_t b2 = b + NW;
-          if (b2 < dend) {
-            const uint32_t rel2 = (uint32_t)(b2 - te.desc_begin) - cur0;
-            const SdbBlockDesc d2 = rel2 < a.dcache_n
-                                      ? dcache[t * a.dcache_n + rel2]
-                                      : a.desc[b2];
-            if (d2.prev_doc < hi && d.len == 128 && d2.len == 128 &&
-                try_block_fused2<1>(pl, d, d2, lane, a.norm_stream, lo,
-                                    hi, num, nc, nl, a.scorer, a.norms,
-                                    a.fb, swin, mwin)) {
-              b += 2 * NW;
-              continue;
-            }
-          }
-        }
-        // prefetch the NEXT block's payload so its decode loads hit L1
-        {
-          const uint64_t nb = b + NW;
-          if (nb < dend) {
-            const uint32_t nrel = (uint32_t)(nb - te.desc_begin) - cur0;
-            const SdbBlockDesc dn = nrel < a.dcache_n
-                                      ? dcache[t * a.dcache_n + nrel]
-                                      : a.desc[nb];
-            if (dn.prev_doc < hi) {
-              const uint32_t* pfp = align_down4(pl + dn.doc_off);
-              const uint32_t pf = pfp[lane];
-              asm volatile("" ::"v"(pf));
-            }
-          }
-        }
-        if (try_block_fused<1>(pl + d.doc_off, d, lane, a.norm_stream, lo,
-                               hi, num, nc, nl, a.scorer, a.norms, a.fb,
-                               swin, mwin)) {
-          b += NW;
+        for (int k = 0; k < 7; ++k) wv[k] = p[k];
+      } else {
+        GlobalWord* p =
+          (GlobalWord*)&a.desc[te.desc_begin + cursors[t] + rel];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) wv[k] = p[k];
+      }
+      // an item is the same for the whole wave: keep it in scalar
+      // registers (the vector file is what this kernel is short of)
+      __builtin_memcpy(wv + 7, &te.payload_begin, 8);
+      __builtin_memcpy(wv + 9, &te.num, 4);
+#pragma unroll
+      for (int k = 0; k < 10; ++k)
+        wv[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)wv[k]);
+      uint64_t pbeg;
+      __builtin_memcpy(&it.d, wv, 28);
+      __builtin_memcpy(&pbeg, wv + 7, 8);
+      __builtin_memcpy(&it.num, wv + 9, 4);
+      it.t = t;
+      it.pl = a.payload + pbeg;
+    };
+    auto pruned = [&](const SweepItem& it) -> bool {  // WAND own-bound skip
+      const float own = score_one(a.scorer, it.num, nc, nl, it.d.max_freq,
+                                  it.d.min_norm) *
+                        a.fbmax * 1.0000019f;
+      return own + (wand_total_ub - wub[it.t]) < gtw;
+    };
+    uint32_t* dbuf = scratch + wave * 384;
+    uint32_t* fbuf = dbuf + 128;
+    uint32_t* nbuf = fbuf + 128;
+
+    for (uint32_t r0 = 0; r0 < nitems; r0 += C) {
+      const uint32_t r1 = min(r0 + C, nitems);
+      // ---- stage 1: decode + score this round's items into their slots.
+      // A wave takes items r0+wave, +NW, ...; two fused-shape items in a
+      // row go through the dual decode (their terms may differ). The next
+      // item's descriptor is read before this item's payload is waited for.
+      uint32_t i = r0 + wave;
+      SweepItem cur;
+      if (i < r1) load_item(i, cur);
+      while (i < r1) {
+        char* slot = stage + (i - r0) * SDB_SLOT_BYTES;
+        const uint32_t i2 = i + NW;
+        const bool has2 = i2 < r1;
+        SweepItem nxt = cur;
+        if (has2) load_item(i2, nxt);
+        if (a.wand && pruned(cur)) {
+          ((uint32_t*)(slot + 512))[lane] = 0xFFFFFFFFu;  // all absent
+          i = i2;
+          cur = nxt;
           continue;
         }
-        decode_doc_block_wave(pl + d.doc_off, d.len, d.prev_doc, lane, dbuf);
-        decode_freq_block_wave(pl + d.freq_off, d.len, lane, fbuf);
-        if (a.norm_stream)
-          decode_freq_block_wave(pl + d.freq_off + (d.flags >> 1),
-                                 d.len, lane, nbuf);
-        for (uint32_t j = lane; j < d.len; j += 64) {
-          const uint32_t doc = dbuf[j];
-          if (doc < lo || doc > hi) continue;
-          const uint32_t freq = fbuf[j];
-          const uint32_t norm = a.norm_stream ? nbuf[j] : a.norms[doc];
-          const float nm = a.fb ? num * a.fb[doc] : num;
-          const float s = score_one(a.scorer, nm, nc, nl, freq, norm);
-          const uint32_t off = doc - lo;
-          swin_add(swin, off, s);  // unique doc within the term
-          mark_match_mask(mwin, off);
+        SlotSink sk;
+        sk.slot[0] = slot;
+        sk.slot[1] = slot + NW * SDB_SLOT_BYTES;
+        sk.mwin = mwin;
+        if (has2 && cur.d.len == 128 && nxt.d.len == 128 &&
+            !(a.wand && pruned(nxt))) {
+          if (try_block_fused2(cur.pl, nxt.pl, cur.d, nxt.d, lane,
+                               a.norm_stream, lo, hi, cur.num, nxt.num, nc,
+                               nl, a.scorer, a.norms, a.fb, sk)) {
+            // (reading the item after the pair ahead of the pair's loads
+            // costs registers at the 128-VGPR cap and lost its A/B arm:
+            // profiles/round_ab_100m_preload.log)
+            i = i2 + NW;
+            if (i < r1) load_item(i, cur);
+            continue;
+          }
         }
-        b += NW;
-      }
-      pf_acc ^= pf_next;  // keep the prefetch loads alive to phase end
-#ifdef SDB_TIMING
-      if (t == 0) SDB_TS(5)  // term-0 phase alone (imbalance diagnosis)
-#endif
-#ifndef SDB_ABLATE_NOBARRIER  // perf ablation: cost of term serialization
-#ifdef SDB_SWEEP_STAGE
-      // raw barrier + lgkmcnt-only wait: __syncthreads() would drain the
-      // in-flight global_load_lds with vmcnt(0) at EVERY phase boundary
-      // (guide: pipelining across barriers); LDS visibility for the
-      // term-major merge order needs only lgkmcnt
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-#else
-      __syncthreads();  // term-major merge order (bit-exact vs oracle)
-#endif
-#endif
-    }
-#ifdef SDB_ABLATE_NOBARRIER
-    __syncthreads();
-#endif
-    asm volatile("" ::"v"(pf_acc));  // waits land here, once per window
-    SDB_TS(1)
-    // advance every term's cursor once per window
-#ifdef SDB_MACH
-    // wave-parallel: wave t ballots over the staged last_docs instead of
-    // lane 0..nterms-1 of wave 0 walking serial dependent LDS reads
-    if (wave < a.nterms) {
-      const uint32_t t = wave;
-      const TermDev te = tstage[t];
-      const uint32_t cur0 = cursors[t];
-      const uint64_t rem = te.desc_end - (te.desc_begin + cur0);
-      const uint32_t avail = rem < a.dcache_n ? (uint32_t)rem : a.dcache_n;
-      uint32_t lastd = 0xFFFFFFFFu;
-      if ((uint32_t)lane < avail)
-        lastd = dcache[t * a.dcache_n + lane].last_doc;
-      const unsigned long long inwin = __ballot(lastd <= hi);
-      const uint32_t adv = (uint32_t)__builtin_ctzll(~inwin);
-      if (lane == 0) {
-        uint32_t cur = cur0 + adv;
-        if (adv == avail) {  // cache exhausted: finish from global descs
-          while (te.desc_begin + cur < te.desc_end &&
-                 a.desc[te.desc_begin + cur].last_doc <= hi)
-            ++cur;
+        // touch the NEXT item's payload so its decode loads hit L1
+        if (has2) {
+          const uint32_t* pfp = align_down4(nxt.pl + nxt.d.doc_off);
+          const uint32_t pf = pfp[lane];
+          asm volatile("" ::"v"(pf));
         }
-        cursors[t] = cur;
+        if (!try_block_fused(cur.pl + cur.d.doc_off, cur.d, lane,
+                             a.norm_stream, lo, hi, cur.num, nc, nl,
+                             a.scorer, a.norms, a.fb, sk)) {
+          const SdbBlockDesc& d = cur.d;
+          decode_doc_block_wave(cur.pl + d.doc_off, d.len, d.prev_doc, lane,
+                                dbuf);
+          decode_freq_block_wave(cur.pl + d.freq_off, d.len, lane, fbuf);
+          if (a.norm_stream)
+            decode_freq_block_wave(cur.pl + d.freq_off + (d.flags >> 1),
+                                   d.len, lane, nbuf);
+#pragma unroll
+          for (uint32_t e = 0; e < 2; ++e) {
+            const uint32_t j = (uint32_t)lane + 64u * e;
+            float s = 0.0f;
+            uint32_t off = SDB_SLOT_ABSENT;
+            if (j < d.len) {
+              const uint32_t doc = dbuf[j];
+              if (doc >= lo && doc <= hi) {
+                const uint32_t freq = fbuf[j];
+                const uint32_t norm = a.norm_stream ? nbuf[j] : a.norms[doc];
+                const float nm = a.fb ? cur.num * a.fb[doc] : cur.num;
+                s = score_one(a.scorer, nm, nc, nl, freq, norm);
+                off = doc - lo;
+                mark_match_mask(mwin, off);
+              }
+            }
+            ((float*)slot)[j] = s;
+            ((uint16_t*)(slot + 512))[j] = (uint16_t)off;
+          }
+        }
+        i = i2;
+        cur = nxt;
       }
-    }
-#else
-    if (tid < a.nterms) {
-      const uint32_t t = tid;
-      const TermDev te = tstage[t];
-      uint32_t cur = cursors[t];
-      const uint32_t cur0 = cur;
-      while (te.desc_begin + cur < te.desc_end) {
-        const uint32_t rel = cur - cur0;
-        const uint32_t last = rel < a.dcache_n
-                                ? dcache[t * a.dcache_n + rel].last_doc
-                                : a.desc[te.desc_begin + cur].last_doc;
-        if (last > hi) break;
-        ++cur;
+      __syncthreads();  // every slot of the round written
+      SDB_TS(1)
+      // ---- stage 2: merge, LDS only. Term by term (the fp32 add order
+      // per doc, bit-exact vs the oracle); docs are unique within a term,
+      // so the adds of one pass never meet. A thread takes an entry pair.
+      for (uint32_t t = 0; t < a.nterms; ++t) {
+        const uint32_t tb =
+          (uint32_t)__builtin_amdgcn_readlane((int)ipre_excl, (int)t);
+        const uint32_t te_ =
+          (uint32_t)__builtin_amdgcn_readlane((int)ipre_incl, (int)t);
+        const uint32_t i0 = max(tb, r0), i1 = min(te_, r1);
+        if (i0 >= i1) continue;  // uniform over the workgroup
+        const char* base = stage + (i0 - r0) * SDB_SLOT_BYTES;
+        const uint32_t npair = (i1 - i0) * 64u;
+        for (uint32_t p = tid; p < npair; p += NTH) {
+          const char* sl = base + (p >> 6) * SDB_SLOT_BYTES;
+          const uint32_t l = p & 63u;
+          const float2 v = ((const float2*)sl)[l];
+          const uint32_t o = ((const uint32_t*)(sl + 512))[l];
+          const uint32_t o0 = o & 0xFFFFu, o1 = o >> 16;
+          if (o0 != SDB_SLOT_ABSENT) swin_add(swin, o0, v.x);
+          if (o1 != SDB_SLOT_ABSENT) swin_add(swin, o1, v.y);
+        }
+        __syncthreads();  // next term's adds, next round's slot writes
       }
-      cursors[t] = cur;
+      SDB_TS(2)
     }
-#endif
-    __syncthreads();  // cursors visible to the next-window prefetch below
+    // advance every term's cursor once per window (nothing reads cursors
+    // or iadv again before the barrier that ends the window)
+    if (tid < a.nterms) cursors[tid] += iadv[tid];
 
     // ---- ONE sparse sweep over set bits: match count (popcount),
     // candidate count vs the staged threshold snapshot, sampled histogram
     uint32_t tbin_w = shared_misc[0];
-    // next-window prefetch: touch each term's next block payload for this
-    // wave under the sweep/tau/append tail (consumed at window end)
-    uint32_t pf_w = 0;
-    if (w + 1 < w_hi && wave < a.nterms) {
-      const uint32_t t = wave;
-      const TermDev te = tstage[t];
-      const uint32_t ncur = cursors[t];  // post-advance (barrier above)
-      const uint64_t nb = te.desc_begin + ncur;
-      if (nb < te.desc_end) {
-        const uint32_t* pfp = align_down4(a.payload + te.payload_begin +
-                                          a.desc[nb].doc_off);
-        pf_w = pfp[lane] + pfp[lane + 64];
-      }
-    }
+    // (the next-window payload prefetch that sat here lost its A/B arm
+    // once stage 1 covered the first fetch: profiles/round_ab_100m_pfw.log)
     const uint32_t nw_act = (wlen + 63u) / 64u;
     uint32_t my_matches = 0;
     uint32_t my_cnt = 0;
@@ -1732,7 +1692,7 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
     for (int off = 32; off; off >>= 1) wm += __shfl_down(wm, off, 64);
     if (lane == 0) shared_misc[2 + wave] = wm;
     __syncthreads();
-    SDB_TS(2)
+    SDB_TS(3)
 
     if (a.fcol)
       for (uint32_t i = tid; i < 2 * a.nbuckets; i += NTH)
@@ -1787,7 +1747,7 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
       for (uint32_t v = 0; v < NW; ++v) total_m += shared_misc[2 + v];
       wg_matches += total_m;
     }
-    SDB_TS(3)
+    SDB_TS(4)
 
     // first window: refresh the (still ~0) snapshot from the just-derived
     // global bin and recount, or the whole grid appends every match
@@ -1849,9 +1809,8 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
           }
         } while (word);
       }
-    asm volatile("" ::"v"(pf_w));  // next-window prefetch lands
     __syncthreads();  // window state reused next iteration
-    SDB_TS(4)
+    SDB_TS(5)
   }
   if (tid == 0 && wg_matches) atomicAdd(a.total_matches, wg_matches);
 #ifdef SDB_TIMING
@@ -2444,18 +2403,58 @@ bool launch_sweep(const SweepGeom& g, bool wide, dim3 grid, size_t lds,
   return false;
 }
 
-// fixed (non-dcache) LDS bytes of one sweep workgroup
-size_t sweep_lds_fixed(const SweepGeom& g) {
-  size_t b = (size_t)g.wd * 4 + g.wd / 8 + (g.nth / 64) * 1536 +
-             SDB_HIST_BINS * 4 + (2 + g.nth / 64) * 4 +
-             2 * SDB_MAX_TERMS * 4 + sizeof(TermDev) * SDB_MAX_TERMS +
-             16 * SDB_MAX_BUCKETS;
-#ifdef SDB_SWEEP_STAGE
-  b += (g.nth / 64) * SDB_STG_TERMS * 4   // smeta
-       + 16                               // alignment pad
-       + (g.nth / 64) * SDB_STG_TERMS * SDB_STG_CAP;
-#endif
-  return b;
+// LDS bytes of one sweep workgroup in front of the descriptor cache (the
+// layout at the top of topk_sweep_kernel): the term table is sized to the
+// plan and the bucket accumulators exist for hybrid plans only, so that the
+// posting stage gets what they leave
+size_t sweep_lds_fixed(const SweepGeom& g, uint32_t nterms, bool hybrid) {
+  return (size_t)g.wd * 4 + g.wd / 8 + (g.nth / 64) * 1536 +
+         SDB_HIST_BINS * 4 + (2 + g.nth / 64) * 4 + 4 * SDB_MAX_TERMS * 4 +
+         sizeof(TermDev) * nterms + (hybrid ? 16 * SDB_MAX_BUCKETS : 0);
+}
+
+// LDS plan of one sweep launch. The posting stage (round_items slots of
+// SDB_SLOT_BYTES) takes what swin/mwin/scratch/dcache leave within 160 KB,
+// up to a slot per 512 window docs plus one per term: the items of a plan
+// whose postings cover a quarter of the window. Wide plans shrink the
+// descriptor cache until at least one slot per wave fits. The stage never
+// costs a resident workgroup: the geometries that run several workgroups
+// per CU (12288x512 and smaller) keep the count they reach with the
+// minimum stage of one slot per wave, and get only the slots that fit
+// beside it. A window with more items than slots runs in rounds.
+// SDB_SWEEP_ROUND_ITEMS (read per call, like SDB_SWEEP_GEOM) clamps the
+// slot count downward, never below one per wave.
+struct SweepLds {
+  bool ok;
+  uint32_t dcache_n, round_items, wgs_per_cu;
+  size_t bytes;
+};
+SweepLds plan_sweep_lds(const SweepGeom& g, uint32_t nterms, bool hybrid) {
+  constexpr size_t kLds = 163840;
+  const uint32_t nw = g.nth / 64u;
+  const size_t fixed = sweep_lds_fixed(g, nterms, hybrid);
+  auto total = [&](uint32_t dn, uint32_t c) {
+    return fixed + sizeof(SdbBlockDesc) * dn * nterms + 16 /* stage align */ +
+           (size_t)c * SDB_SLOT_BYTES;
+  };
+  SweepLds p{false, SDB_DESC_CACHE, nw, 1, 0};
+  while (p.dcache_n > 1 && total(p.dcache_n, nw) > kLds) --p.dcache_n;
+  if (total(p.dcache_n, nw) > kLds) return p;
+  const uint32_t wgs = std::min<uint32_t>(
+    (uint32_t)(kLds / total(p.dcache_n, nw)), 32u / nw);  // 32 waves/CU
+  const uint32_t want = g.wd / 512u + nterms;
+  const uint32_t fit =
+    (uint32_t)((kLds / wgs - total(p.dcache_n, 0)) / SDB_SLOT_BYTES);
+  p.round_items = std::max(nw, std::min(want, fit));
+  if (const char* e = getenv("SDB_SWEEP_ROUND_ITEMS")) {
+    const unsigned long v = strtoul(e, nullptr, 10);
+    if (v >= 1 && v < p.round_items)
+      p.round_items = std::max<uint32_t>(nw, (uint32_t)v);
+  }
+  p.bytes = total(p.dcache_n, p.round_items);
+  p.wgs_per_cu = wgs;
+  p.ok = true;
+  return p;
 }
 
 int check_gpu() {
@@ -2940,23 +2939,10 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
       sgeom.nth = nth_;
     }
   }
-  uint32_t s_dcache_n = SDB_DESC_CACHE;
-  size_t s_lds = 0;
-  uint32_t s_wgs_per_cu = 1;
+  SweepLds slds{};
   if (use_sweep) {
-    const size_t fixed = sweep_lds_fixed(sgeom);
-    s_lds = fixed + sizeof(SdbBlockDesc) * s_dcache_n * plan->nterms;
-    const uint32_t wave_cap = 32u / (sgeom.nth / 64u);  // 32 waves/CU
-    s_wgs_per_cu = (uint32_t)(163840 / s_lds);
-    if (s_wgs_per_cu > wave_cap) s_wgs_per_cu = wave_cap;
-    if (s_wgs_per_cu == 0) {  // shrink the desc cache until one WG fits
-      while (s_dcache_n > 1 && s_lds > 163840) {
-        --s_dcache_n;
-        s_lds = fixed + sizeof(SdbBlockDesc) * s_dcache_n * plan->nterms;
-      }
-      if (s_lds > 163840) use_sweep = false;
-      s_wgs_per_cu = 1;
-    }
+    slds = plan_sweep_lds(sgeom, plan->nterms, hybrid);
+    if (!slds.ok) use_sweep = false;
   }
 
   // hybrid bucket form, once per call (sdb_internal.h)
@@ -3055,12 +3041,13 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
       continue;
     }
     if (use_sweep) {
-      a.dcache_n = s_dcache_n;
+      a.dcache_n = slds.dcache_n;
+      a.round_items = slds.round_items;
       const uint32_t nwin = (seg->hdr.doc_count + sgeom.wd - 1) / sgeom.wd;
-      uint32_t ngrid = 256u * s_wgs_per_cu;
+      uint32_t ngrid = 256u * slds.wgs_per_cu;
       if (ngrid > nwin) ngrid = nwin;
-      if (!launch_sweep(sgeom, wide_span, dim3(ngrid), s_lds, ctx->stream, a,
-                        d_tslot))
+      if (!launch_sweep(sgeom, wide_span, dim3(ngrid), slds.bytes,
+                        ctx->stream, a, d_tslot))
         return SDB_ERR_INVALID;  // unknown SDB_SWEEP_GEOM instantiation
       HIP_CHECK(hipGetLastError());
       continue;
@@ -3164,8 +3151,11 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
     unsigned long long tdbg[6];
     hipMemcpy(tdbg, ctx->d_buckets, 48, hipMemcpyDeviceToHost);
     fprintf(stderr,
-            "[timing cyc/WG avg] zero+stage=%llu phases=%llu hist=%llu "
-            "tau=%llu append=%llu term0=%llu\n",
+            use_sweep
+              ? "[timing cyc/WG avg] zero+stage=%llu stage1=%llu stage2=%llu "
+                "sweep=%llu tau=%llu append=%llu\n"
+              : "[timing cyc/WG avg] zero+stage=%llu phases=%llu hist=%llu "
+                "tau=%llu append=%llu term0=%llu\n",
             tdbg[0] / 256, tdbg[1] / 256, tdbg[2] / 256, tdbg[3] / 256,
             tdbg[4] / 256, tdbg[5] / 256);
   }
@@ -3281,23 +3271,10 @@ static int exec_topk_batch_impl(
       (uint32_t)(room / (sizeof(SdbBlockDesc) * plan->nterms));
     if (fit < gen_dcache_n) gen_dcache_n = fit;
   }
-  uint32_t s_dcache_n = SDB_DESC_CACHE;
-  size_t s_lds = 0;
-  uint32_t s_wgs_per_cu = 1;
+  SweepLds slds{};
   if (use_sweep) {
-    const size_t fixed = sweep_lds_fixed(sgeom);
-    s_lds = fixed + sizeof(SdbBlockDesc) * s_dcache_n * plan->nterms;
-    const uint32_t wave_cap = 32u / (sgeom.nth / 64u);
-    s_wgs_per_cu = (uint32_t)(163840 / s_lds);
-    if (s_wgs_per_cu > wave_cap) s_wgs_per_cu = wave_cap;
-    if (s_wgs_per_cu == 0) {
-      while (s_dcache_n > 1 && s_lds > 163840) {
-        --s_dcache_n;
-        s_lds = fixed + sizeof(SdbBlockDesc) * s_dcache_n * plan->nterms;
-      }
-      if (s_lds > 163840) use_sweep = false;
-      s_wgs_per_cu = 1;
-    }
+    slds = plan_sweep_lds(sgeom, plan->nterms, hybrid);
+    if (!slds.ok) use_sweep = false;
   }
 
   // per-set device state inside d_qmisc. Each atomically-updated word
@@ -3401,13 +3378,14 @@ static int exec_topk_batch_impl(
         continue;
       }
       if (use_sweep) {
-        a.dcache_n = s_dcache_n;
+        a.dcache_n = slds.dcache_n;
+        a.round_items = slds.round_items;
         const uint32_t nwin =
           (seg->hdr.doc_count + sgeom.wd - 1) / sgeom.wd;
-        uint32_t ngrid = 256u * s_wgs_per_cu;
+        uint32_t ngrid = 256u * slds.wgs_per_cu;
         if (ngrid > nwin) ngrid = nwin;
-        if (!launch_sweep(sgeom, wide_span, dim3(ngrid), s_lds, ctx->stream, a,
-                          d_tslot))
+        if (!launch_sweep(sgeom, wide_span, dim3(ngrid), slds.bytes,
+                          ctx->stream, a, d_tslot))
           return SDB_ERR_INVALID;
         HIP_CHECK(hipGetLastError());
         continue;

@@ -4,12 +4,17 @@ per execute call, so one resident corpus serves every variant).
 
   python tools/ab_sweep.py [--docs 100000000] [--steps 10] [--warmup 2]
          [--geoms 0,24576x1024,...] [--k 1000] [--wand]
-         [--libs name=path,...] [--rounds N] [--skip-default]
+         [--libs name=path[@C],...] [--rounds N] [--skip-default]
+         [--sels 0.10,0.05,0.02,0.01]
 
 Prints one line per library and geometry: ms/step, kernel ms, postings/s,
 and the hit-set parity against the first variant measured. With --rounds N
 every arm is measured N times, arms alternating within each round, and the
-line carries the median and the min..max spread over rounds.
+line carries the median and the min..max spread over rounds. A library
+given as name=path@C is measured with SDB_SWEEP_ROUND_ITEMS=C (the sweep
+kernel's posting-stage capacity clamped to C slots), so one library can
+appear as several arms. --sels gives the plan: one OR term per selectivity
+(e.g. 0.6,0.5 for a dense two-term plan).
 """
 
 import argparse
@@ -34,25 +39,30 @@ def main():
     ap.add_argument("--geoms", default=DEFAULT_GEOMS)
     ap.add_argument("--wand", action="store_true")
     ap.add_argument("--libs", default="",
-                    help="name=path,... : extra GPU libs to compare on the "
-                         "same corpus (fresh context + segment reload per "
-                         "lib; ablation/timing builds)")
+                    help="name=path[@C],... : extra GPU libs to compare on "
+                         "the same corpus (fresh context + segment reload "
+                         "per lib; ablation/timing builds); @C runs the arm "
+                         "with SDB_SWEEP_ROUND_ITEMS=C")
     ap.add_argument("--rounds", type=int, default=1,
                     help="measure every arm N times, the arms alternating "
                          "round by round on the one resident corpus; prints "
                          "per arm the median and min..max over rounds of "
                          "kernel ms and ms/step")
+    ap.add_argument("--sels", default="0.10,0.05,0.02,0.01",
+                    help="term selectivities of the synthetic corpus; the "
+                         "plan is the OR of all of them")
     ap.add_argument("--skip-default", action="store_true",
                     help="with --libs: leave the in-tree library out")
     args = ap.parse_args()
 
-    sels = [0.10, 0.05, 0.02, 0.01]
+    sels = [float(x) for x in args.sels.split(",")]
+    nt = len(sels)
     t0 = time.time()
     blob = sa.build_synth_segment(43, 1, args.docs, sels)
     print(f"build {time.time()-t0:.1f}s blob {len(blob)/1e6:.0f}MB",
           flush=True)
-    term_idx = [0, 1, 2, 3]
-    boosts = [1.0] * 4
+    term_idx = list(range(nt))
+    boosts = [1.0] * nt
 
     import ctypes as CT
 
@@ -75,12 +85,15 @@ def main():
     vw = _View()
     host.sdb_host_segment_parse(v.ctypes.data_as(CT.c_void_p),
                                 CT.c_uint64(len(v)), CT.byref(vw))
-    terms = CT.cast(vw.terms, CT.POINTER(_Term * 4)).contents
-    postings = sum(terms[t].df for t in range(4))
+    terms = CT.cast(vw.terms, CT.POINTER(_Term * nt)).contents
+    postings = sum(terms[t].df for t in range(nt))
 
     libspecs = [("default", None)]
+    round_items = {}
     for ent in (args.libs.split(",") if args.libs else []):
         nm, pth = ent.split("=", 1)
+        if "@" in pth:
+            pth, round_items[nm] = pth.rsplit("@", 1)
         libspecs.append((nm, pth))
     if args.skip_default and len(libspecs) > 1:
         libspecs = libspecs[1:]
@@ -99,7 +112,11 @@ def main():
         ctx = sa.GpuContext(0)
         arms.append((libname, ctx, ctx.load_segment(blob)))
 
-    def measure(ctx, seg):
+    def measure(libname, ctx, seg):
+        if libname in round_items:
+            os.environ["SDB_SWEEP_ROUND_ITEMS"] = round_items[libname]
+        else:
+            os.environ.pop("SDB_SWEEP_ROUND_ITEMS", None)
         for _ in range(args.warmup):
             hits, total = ctx.execute_topk([seg], term_idx, boosts, args.k,
                                            wand=args.wand)
@@ -129,7 +146,7 @@ def main():
         parity = {}
         for _ in range(args.rounds):
             for libname, ctx, seg in arms:   # arms alternate within a round
-                sms, kms, cur = measure(ctx, seg)
+                sms, kms, cur = measure(libname, ctx, seg)
                 step_ms[libname].append(sms)
                 kern_ms[libname].append(kms)
                 if ref is None:
