@@ -1310,7 +1310,9 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
   uint32_t* gh = a.ghist + (blockIdx.x & 7u) * SDB_HIST_BINS;
   unsigned long long wg_matches = 0;
 #ifdef SDB_TIMING
-  // slots: 0 zero+stage, 1 stage 1, 2 stage 2, 3 sweep, 4 tau, 5 append
+  // slots: 0 zero (window start), 1 stage 1, 2 stage 2, 3 sweep, 4 tail
+  // (sweep barrier to reservation barrier: reserve, derive, next-window
+  // fetch), 5 append
   unsigned long long t_acc[6] = {0, 0, 0, 0, 0, 0};
   long long t_mark = clock64();
 #define SDB_TS(idx)                                        \
@@ -1340,6 +1342,62 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
       te.desc_begin);
   }
   __syncthreads();
+
+  // Count and stage the items of the window that ends at doc hi_n, from the
+  // cursors as they stand, on waves w0 and up. Term t contributes the blocks
+  // from its cursor whose prev_doc < hi_n (icnt); those of them whose
+  // last_doc <= hi_n are done after that window (iadv). Both sets are
+  // prefixes of the term's block list, so a ballot per 64 blocks counts
+  // them; a dense term takes several. Then term t's next dcache_n descs
+  // from its cursor go to dcache as coalesced u32 reads. The caller's next
+  // barrier publishes icnt, iadv and dcache. Window w + 1 is fetched in the
+  // tail of window w, beside the tail's own round trips (the cursors are
+  // final there, and nothing reads icnt, iadv or dcache after stage 2);
+  // a workgroup's first window is fetched ahead of the loop.
+  auto fetch_window = [&](uint32_t hi_n, uint32_t w0) {
+    if (wave < w0) return;
+    const uint32_t nwv = NW - w0;
+    for (uint32_t t = wave - w0; t < a.nterms; t += nwv) {
+      const TermDev te = tstage[t];
+      uint64_t b = te.desc_begin + cursors[t] + (uint32_t)lane;
+      uint32_t cnt = 0, adv = 0;
+      for (;;) {
+        uint32_t prev = 0xFFFFFFFFu, last = 0xFFFFFFFFu;
+        if (b < te.desc_end) {
+          prev = a.desc[b].prev_doc;
+          last = a.desc[b].last_doc;
+        }
+        const uint32_t c = (uint32_t)__popcll(__ballot(prev < hi_n));
+        adv += (uint32_t)__popcll(__ballot(last <= hi_n));
+        cnt += c;
+        if (c < 64u) break;
+        b += 64u;
+      }
+      if (lane == 0) {
+        icnt[t] = cnt;
+        iadv[t] = adv;
+      }
+    }
+    const uint32_t words_per_term = a.dcache_n * 7u;
+    for (uint32_t i = tid - w0 * 64u; i < a.nterms * words_per_term;
+         i += nwv * 64u) {
+      const uint32_t t = i / words_per_term;
+      const uint32_t wrd = i % words_per_term;
+      const TermDev te = tstage[t];
+      const uint64_t b0 = te.desc_begin + cursors[t];
+      const uint32_t avail =
+        (uint32_t)(te.desc_end > b0 ? te.desc_end - b0 : 0);
+      if (wrd < avail * 7u)
+        ((uint32_t*)&dcache[t * a.dcache_n])[wrd] =
+          ((const uint32_t*)&a.desc[b0])[wrd];
+    }
+  };
+  fetch_window((uint32_t)min((uint64_t)(w_lo + 1u) * WD,
+                             (uint64_t)a.doc_count), 0);
+  if (tid == 0)
+    shared_misc[0] = __hip_atomic_load(a.gthresh, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();  // the first window's WAND bound scan reads dcache
   const float nc = tstage[0].nc, nl = tstage[0].nl;  // plan-wide
 
   for (uint32_t w = w_lo; w < w_hi; ++w) {
@@ -1350,60 +1408,15 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
     const bool derive = ((w & 3u) == 0) || (w < w_lo + 2);
     uint32_t my_excl_snap = 0;
 
-    // count this window's items, wave-parallel from the global descriptors
-    // (no wait on the staging below): term t contributes the blocks from
-    // its cursor whose prev_doc < hi (icnt); those of them whose last_doc
-    // <= hi are done after this window (iadv). Both sets are prefixes of
-    // the term's block list, so a ballot per 64 blocks counts them; a dense
-    // term takes several.
-    for (uint32_t t = wave; t < a.nterms; t += NW) {
-      const TermDev te = tstage[t];
-      uint64_t b = te.desc_begin + cursors[t] + (uint32_t)lane;
-      uint32_t cnt = 0, adv = 0;
-      for (;;) {
-        uint32_t prev = 0xFFFFFFFFu, last = 0xFFFFFFFFu;
-        if (b < te.desc_end) {
-          prev = a.desc[b].prev_doc;
-          last = a.desc[b].last_doc;
-        }
-        const uint32_t c = (uint32_t)__popcll(__ballot(prev < hi));
-        adv += (uint32_t)__popcll(__ballot(last <= hi));
-        cnt += c;
-        if (c < 64u) break;
-        b += 64u;
-      }
-      if (lane == 0) {
-        icnt[t] = cnt;
-        iadv[t] = adv;
-      }
-    }
-
+    // the window start touches LDS only: this window's item counts, staged
+    // descriptors and threshold snapshot were fetched in the previous
+    // window's tail (or ahead of the loop) and published by its barriers
     for (uint32_t i = tid; i < WD; i += NTH) swin[i] = 0.0f;
     for (uint32_t i = tid; i < NWORDS; i += NTH) mwin[i] = 0ull;
     if (derive)
       for (uint32_t i = tid; i < SDB_HIST_BINS; i += NTH) hist[i] = 0;
     if (a.fcol)
       for (uint32_t i = tid; i < 2 * a.nbuckets; i += NTH) lbuck[i] = 0;
-    // stage this window's descriptors: term t's next dcache_n descs from
-    // its cursor, as coalesced u32 reads
-    {
-      const uint32_t words_per_term = a.dcache_n * 7u;
-      for (uint32_t i = tid; i < a.nterms * words_per_term; i += NTH) {
-        const uint32_t t = i / words_per_term;
-        const uint32_t wrd = i % words_per_term;
-        const TermDev te = tstage[t];
-        const uint64_t b0 = te.desc_begin + cursors[t];
-        const uint32_t avail =
-          (uint32_t)(te.desc_end > b0 ? te.desc_end - b0 : 0);
-        if (wrd < avail * 7u)
-          ((uint32_t*)&dcache[t * a.dcache_n])[wrd] =
-            ((const uint32_t*)&a.desc[b0])[wrd];
-      }
-    }
-    if (tid == 0)
-      shared_misc[0] = __hip_atomic_load(a.gthresh, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT);
-    if (a.wand) __syncthreads();  // wub scan reads other threads' staging
     if (a.wand) {
       // per-term window score upper bounds, WAVE-parallel: lane l reads
       // staged desc l of the wave's term and the bound max-reduces via
@@ -1615,7 +1628,8 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
       SDB_TS(2)
     }
     // advance every term's cursor once per window (nothing reads cursors
-    // or iadv again before the barrier that ends the window)
+    // or iadv again before the sweep barrier; behind it the tail fetches
+    // the next window from the advanced cursors)
     if (tid < a.nterms) cursors[tid] += iadv[tid];
 
     // ---- ONE sparse sweep over set bits: match count (popcount),
@@ -1694,52 +1708,106 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
     __syncthreads();
     SDB_TS(3)
 
+    // ---- window tail ("Window tail"): every global round trip
+    // of the tail is issued here, right behind the sweep barrier, by a
+    // different wave, so that they overlap instead of queueing on wave 0:
+    //   wave 0      the candidate-space reservation (a returning atomic)
+    //   wave DRV    the threshold derivation and the next window's snapshot
+    //   waves 2..   the next window's item counts and staged descriptors
+    // The append filters against tbin_w, the snapshot taken before this
+    // window started, so it waits for the reservation alone. Only a
+    // workgroup's first window (snapshot still ~0) keeps derive -> refresh
+    // -> recount -> reserve in a row.
+    constexpr uint32_t DRV = 1;  // NW >= 4 for every compiled geometry
+    const bool first = w == w_lo;
+    uint32_t block_total = 0, wave_base = 0, resv = 0;
+    auto count_and_reserve = [&]() {
+      for (uint32_t v = 0; v < NW; ++v) {
+        const uint32_t c = scratch[NTH + v];
+        block_total += c;
+        wave_base += v < wave ? c : 0u;
+      }
+      // ONE cursor atomicAdd per workgroup per window; its value is waited
+      // for only at the store to shared_misc[1] below
+      if (tid == 0 && block_total)
+        resv = atomicAdd(a.cand_count, block_total);
+    };
+    if (!first) count_and_reserve();
+    // the next window's counts and descriptors, on the waves that neither
+    // reserve nor derive: the sweep barrier published the advanced cursors
+    if (w + 1 < w_hi) fetch_window(hi + min(WD, a.doc_count - hi), DRV + 1);
+
     if (a.fcol)
       for (uint32_t i = tid; i < 2 * a.nbuckets; i += NTH)
         if (lbuck[i]) atomicAdd(&a.bucket_out[i], lbuck[i]);
 
-    // merge window histogram into the per-XCD global shard, derive the
-    // threshold bin from the global suffix counts (identical to the
-    // general kernel; see score_bin for the exactness argument)
-    const uint32_t known_bin = __hip_atomic_load(
-      a.gthresh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // merge the window histogram into the per-XCD global shard. Bins below
+    // the snapshot are skipped: the snapshot is <= the live threshold, so a
+    // few bins under the threshold may still be merged, and those never
+    // reach the suffix count that decides the bin.
     if (derive)
       for (uint32_t b = tid; b < SDB_HIST_BINS; b += NTH)
-        if (b >= known_bin && hist[b]) atomicAdd(&gh[b], hist[b]);
-    if (derive && wave == 0) {
-      uint32_t part = 0;
-      if (SDB_HIST_BINS - 1 - 4 * (uint32_t)lane + 3 >= known_bin) {
+        if (b >= tbin_w && hist[b]) atomicAdd(&gh[b], hist[b]);
+
+    // threshold bin from the global suffix counts (see score_bin for the
+    // exactness argument). A lane loads its four bins' eight shards once,
+    // all 32 loads in flight together with the live-threshold load, and the
+    // winner lane walks the four sums it holds: counts only grow, so sums
+    // read a moment earlier give an equal or lower bin, which is still a
+    // valid lower bound.
+    uint32_t snap_next = tbin_w;
+    if (wave == DRV) {
+      // the live threshold: next window's snapshot, and what keeps a
+      // derived bin that is no news from becoming an atomic. The first
+      // window reads it after its derive instead (below).
+      uint32_t gth = tbin_w;
+      if (!first)
+        gth = __hip_atomic_load(a.gthresh, __ATOMIC_RELAXED,
+                                __HIP_MEMORY_SCOPE_AGENT);
+      uint32_t binfloor = 0;
+      bool winner = false;
+      if (derive) {
+        uint32_t bsum[4] = {0, 0, 0, 0};
+        if (SDB_HIST_BINS - 1 - 4 * (uint32_t)lane + 3 >= tbin_w) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint32_t b = SDB_HIST_BINS - 4 * lane - 4 + j;
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t b = SDB_HIST_BINS - 4 * lane - 4 + j;
 #pragma unroll
-          for (int sh = 0; sh < 8; ++sh)
-            part += __hip_atomic_load(&a.ghist[sh * SDB_HIST_BINS + b],
-                                      __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      const uint32_t suff_incl = wave_incl_scan(part, lane);
-      const uint32_t suff_prev = __shfl_up(suff_incl, 1, 64);
-      const bool winner =
-        suff_incl >= a.k && (lane == 0 || suff_prev < a.k);
-      if (winner) {
-        uint32_t cum = suff_incl - part;
-        uint32_t binfloor = 0;
-        for (int b = (int)(SDB_HIST_BINS - 1 - 4 * lane);; --b) {
-          uint32_t add = 0;
-#pragma unroll
-          for (int sh = 0; sh < 8; ++sh)
-            add += __hip_atomic_load(&a.ghist[sh * SDB_HIST_BINS + b],
-                                     __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-          cum += add;
-          if (cum >= a.k) {
-            binfloor = (uint32_t)b;
-            break;
+            for (int sh = 0; sh < 8; ++sh)
+              bsum[j] += __hip_atomic_load(&a.ghist[sh * SDB_HIST_BINS + b],
+                                           __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
           }
         }
-        if (binfloor > known_bin) atomicMax(a.gthresh, binfloor);
+        const uint32_t part = bsum[0] + bsum[1] + bsum[2] + bsum[3];
+        const uint32_t suff_incl = wave_incl_scan(part, lane);
+        const uint32_t suff_prev = __shfl_up(suff_incl, 1, 64);
+        winner = suff_incl >= a.k && (lane == 0 || suff_prev < a.k);
+        if (winner) {
+          uint32_t cum = suff_incl - part;
+#pragma unroll
+          for (int j = 3; j >= 0; --j) {
+            const bool below = cum < a.k;
+            cum += bsum[j];
+            if (below && cum >= a.k)
+              binfloor = SDB_HIST_BINS - 4 * (uint32_t)lane - 4 + (uint32_t)j;
+          }
+          if (binfloor > gth) atomicMax(a.gthresh, binfloor);
+        }
+      }
+      if (first) {
+        // same wave, same address, program order: this load sees the
+        // atomicMax above
+        if (lane == 0)
+          shared_misc[0] = __hip_atomic_load(a.gthresh, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+        // max(live value, own result) without a second trip: what the
+        // reload behind the atomicMax would have returned, or older
+        uint32_t nb = winner && binfloor > gth ? binfloor : gth;
+        const unsigned long long wmask = __ballot(winner);
+        if (wmask) nb = __shfl(nb, (int)__builtin_ctzll(wmask), 64);
+        snap_next = nb;
       }
     }
     if (wave == 0 && lane == 0) {
@@ -1747,14 +1815,10 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
       for (uint32_t v = 0; v < NW; ++v) total_m += shared_misc[2 + v];
       wg_matches += total_m;
     }
-    SDB_TS(4)
 
     // first window: refresh the (still ~0) snapshot from the just-derived
     // global bin and recount, or the whole grid appends every match
-    if (w == w_lo) {
-      if (tid == 0)
-        shared_misc[0] = __hip_atomic_load(a.gthresh, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
+    if (first) {
       __syncthreads();
       tbin_w = shared_misc[0];
       uint32_t cnt2 = 0;
@@ -1773,18 +1837,19 @@ void topk_sweep_kernel(WindowArgs a, const TermDev* __restrict__ terms) {
       if (lane == 63) scratch[NTH + wave] = incl2;
       my_excl_snap = incl2 - cnt2;
       __syncthreads();
+      count_and_reserve();
     }
+    if (tid == 0) shared_misc[1] = resv;
+    __syncthreads();
+    SDB_TS(4)
+
+    // next window's snapshot: every thread took this window's into tbin_w
+    // before the sweep, and nothing reads the word again before the next
+    // window's first barrier
+    if (!first && tid == DRV * 64u) shared_misc[0] = snap_next;
 
     // append candidates (sparse walk, only when the window holds any)
-    uint32_t wave_base = 0;
-    for (uint32_t v = 0; v < wave; ++v) wave_base += scratch[NTH + v];
     const uint32_t my_excl = wave_base + my_excl_snap;
-    uint32_t block_total = 0;
-    for (uint32_t v = 0; v < NW; ++v) block_total += scratch[NTH + v];
-    if (tid == 0)
-      shared_misc[1] =
-        block_total ? atomicAdd(a.cand_count, block_total) : 0u;
-    __syncthreads();
     const uint32_t cbase = shared_misc[1];
     if (cbase + block_total > a.cand_cap) {
       if (tid == 0) atomicExch(a.overflow, 1u);
@@ -2457,6 +2522,22 @@ SweepLds plan_sweep_lds(const SweepGeom& g, uint32_t nterms, bool hybrid) {
   return p;
 }
 
+// Grid of one sweep launch: every CU's resident workgroups, at most one
+// per window. SDB_SWEEP_GRID=N (read per call, like SDB_SWEEP_ROUND_ITEMS)
+// clamps it downward, so that a small corpus can make a workgroup run many
+// windows (the derive cadence and the window-to-window hand-over otherwise
+// need tens of millions of docs). 0, a non-number and a value above the
+// default are ignored.
+uint32_t sweep_grid(const SweepLds& p, uint32_t nwin) {
+  uint32_t ngrid = 256u * p.wgs_per_cu;
+  if (const char* e = getenv("SDB_SWEEP_GRID")) {
+    char* end = nullptr;
+    const unsigned long v = strtoul(e, &end, 10);
+    if (end != e && *end == '\0' && v >= 1 && v < ngrid) ngrid = (uint32_t)v;
+  }
+  return std::min(ngrid, nwin);
+}
+
 int check_gpu() {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -3044,8 +3125,8 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
       a.dcache_n = slds.dcache_n;
       a.round_items = slds.round_items;
       const uint32_t nwin = (seg->hdr.doc_count + sgeom.wd - 1) / sgeom.wd;
-      uint32_t ngrid = 256u * slds.wgs_per_cu;
-      if (ngrid > nwin) ngrid = nwin;
+      const uint32_t ngrid = sweep_grid(slds, nwin);
+      ctx->last_sweep_grid = ngrid;
       if (!launch_sweep(sgeom, wide_span, dim3(ngrid), slds.bytes,
                         ctx->stream, a, d_tslot))
         return SDB_ERR_INVALID;  // unknown SDB_SWEEP_GEOM instantiation
@@ -3152,8 +3233,8 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
     hipMemcpy(tdbg, ctx->d_buckets, 48, hipMemcpyDeviceToHost);
     fprintf(stderr,
             use_sweep
-              ? "[timing cyc/WG avg] zero+stage=%llu stage1=%llu stage2=%llu "
-                "sweep=%llu tau=%llu append=%llu\n"
+              ? "[timing cyc/WG avg] zero=%llu stage1=%llu stage2=%llu "
+                "sweep=%llu tail=%llu append=%llu\n"
               : "[timing cyc/WG avg] zero+stage=%llu phases=%llu hist=%llu "
                 "tau=%llu append=%llu term0=%llu\n",
             tdbg[0] / 256, tdbg[1] / 256, tdbg[2] / 256, tdbg[3] / 256,
@@ -3382,8 +3463,8 @@ static int exec_topk_batch_impl(
         a.round_items = slds.round_items;
         const uint32_t nwin =
           (seg->hdr.doc_count + sgeom.wd - 1) / sgeom.wd;
-        uint32_t ngrid = 256u * slds.wgs_per_cu;
-        if (ngrid > nwin) ngrid = nwin;
+        const uint32_t ngrid = sweep_grid(slds, nwin);
+        ctx->last_sweep_grid = ngrid;
         if (!launch_sweep(sgeom, wide_span, dim3(ngrid), slds.bytes,
                           ctx->stream, a, d_tslot))
           return SDB_ERR_INVALID;
@@ -3715,6 +3796,14 @@ int sdb_gpu_last_stats(SdbGpuCtx* ctx, double* kernel_ms, unsigned* ncand,
   if (gtau) *gtau = ctx->last_gtau;
   if (readback_ms) *readback_ms = ctx->last_readback_ms;
   if (select_ms) *select_ms = ctx->last_select_ms;
+  return SDB_OK;
+}
+
+// workgroups of the last sweep-kernel launch on this context, per-step or
+// batch (0 before the first): what SDB_SWEEP_GRID came to
+int sdb_gpu_last_sweep_grid(SdbGpuCtx* ctx, unsigned* grid) {
+  if (!ctx || !grid) return SDB_ERR_INVALID;
+  *grid = ctx->last_sweep_grid;
   return SDB_OK;
 }
 

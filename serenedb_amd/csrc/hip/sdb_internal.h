@@ -98,6 +98,7 @@ struct SdbGpuCtx {
   double last_kernel_ms;   // read back via sdb_gpu_last_kernel_ms
   // breakdown of the last execute_topk (sdb_gpu_last_stats)
   unsigned last_ncand;
+  unsigned last_sweep_grid;  // sdb_gpu_last_sweep_grid
   float last_gtau;
   double last_readback_ms;
   double last_select_ms;

@@ -8,9 +8,11 @@ per execute call, so one resident corpus serves every variant).
          [--sels 0.10,0.05,0.02,0.01]
 
 Prints one line per library and geometry: ms/step, kernel ms, postings/s,
-and the hit-set parity against the first variant measured. With --rounds N
-every arm is measured N times, arms alternating within each round, and the
-line carries the median and the min..max spread over rounds. A library
+the candidate count of the last step (what the kernel appended and the host
+read back) and the hit-set parity against the first variant measured. With
+--rounds N every arm is measured N times, arms alternating within each
+round, and the line carries the median and the min..max spread over rounds,
+of the candidate count too. A library
 given as name=path@C is measured with SDB_SWEEP_ROUND_ITEMS=C (the sweep
 kernel's posting-stage capacity clamped to C slots), so one library can
 appear as several arms. --sels gives the plan: one OR term per selectivity
@@ -129,9 +131,12 @@ def main():
             ctx._lib.sdb_gpu_last_kernel_ms(ctx._ctx, CT.byref(ms))
             kms += ms.value
         el = time.time() - t1
+        nc = CT.c_uint(0)
+        ctx._lib.sdb_gpu_last_stats(ctx._ctx, None, CT.byref(nc), None, None,
+                                    None)
         cur = (hits["doc"].copy(), hits["score"].view(np.uint32).copy(),
                total)
-        return el * 1000 / args.steps, kms / args.steps, cur
+        return el * 1000 / args.steps, kms / args.steps, cur, nc.value
 
     ref = None
     for geom in args.geoms.split(","):
@@ -143,10 +148,12 @@ def main():
             os.environ["SDB_SWEEP_GEOM"] = geom
         step_ms = {nm: [] for nm, _, _ in arms}
         kern_ms = {nm: [] for nm, _, _ in arms}
+        ncands = {nm: [] for nm, _, _ in arms}
         parity = {}
         for _ in range(args.rounds):
             for libname, ctx, seg in arms:   # arms alternate within a round
-                sms, kms, cur = measure(libname, ctx, seg)
+                sms, kms, cur, nc = measure(libname, ctx, seg)
+                ncands[libname].append(nc)
                 step_ms[libname].append(sms)
                 kern_ms[libname].append(kms)
                 if ref is None:
@@ -160,11 +167,13 @@ def main():
                     parity.setdefault(libname, "OK")
         for libname, _, _ in arms:
             sm, km = step_ms[libname], kern_ms[libname]
+            ncd = ncands[libname]
             if args.rounds == 1:
                 print(f"lib={libname:8s} geom={geom:12s} "
                       f"{sm[0]:8.3f} ms/step "
                       f"kernel {km[0]:7.3f} ms  "
                       f"{postings/sm[0]/1e6:7.2f}G postings/s  "
+                      f"cands {ncd[0]}  "
                       f"parity={parity[libname]}", flush=True)
             else:
                 print(f"lib={libname:8s} geom={geom:12s} "
@@ -174,6 +183,8 @@ def main():
                       f"ms/step median {np.median(sm):7.4f} "
                       f"[{min(sm):7.4f} .. {max(sm):7.4f}]  "
                       f"{postings/np.median(sm)/1e6:7.2f}G postings/s  "
+                      f"cands median {int(np.median(ncd))} "
+                      f"[{min(ncd)} .. {max(ncd)}]  "
                       f"parity={parity[libname]}", flush=True)
 
 
