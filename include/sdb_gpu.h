@@ -184,6 +184,13 @@ typedef struct SdbQueryPlan {
  * (segment, doc) ascending — a deterministic refinement of the reference's
  * unspecified nth_element tie order (DESIGN.md "Determinism").
  *
+ * segment_idx is the index into this call's segs, not the order in which the
+ * segments were loaded; the same handle may appear more than once, and each
+ * occurrence is a segment of its own. nsegs == 0 is SDB_OK with *out_count =
+ * 0 and *total_matches = 0, here and on the batch, count and hybrid entries
+ * (every bucket zero); a filter_boost plan over no segments has no column
+ * maximum and is SDB_ERR_INVALID.
+ *
  * hits must have room for k entries. */
 int sdb_gpu_execute_topk(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
                          uint32_t nsegs, const SdbQueryPlan* plan, uint32_t k,
