@@ -2538,6 +2538,24 @@ uint32_t sweep_grid(const SweepLds& p, uint32_t nwin) {
   return std::min(ngrid, nwin);
 }
 
+// Grid of one general window kernel launch (topk_window_kernel): the
+// resident workgroups the caller worked out from its LDS size, at most one
+// per window. SDB_WINDOW_GRID=N is the same test hook as SDB_SWEEP_GRID for
+// this kernel: read per call, it clamps the grid downward, so that a
+// ten-window corpus can make one workgroup carry its cursors, its derive
+// cadence and its threshold snapshot over all of them. 0, a non-number, a
+// negative value and a value at or above the default are ignored. Not for
+// production.
+uint32_t window_grid(uint32_t wgs_per_cu, uint32_t nwin) {
+  uint32_t ngrid = 256u * wgs_per_cu;
+  if (const char* e = getenv("SDB_WINDOW_GRID")) {
+    char* end = nullptr;
+    const unsigned long v = strtoul(e, &end, 10);
+    if (end != e && *end == '\0' && v >= 1 && v < ngrid) ngrid = (uint32_t)v;
+  }
+  return std::min(ngrid, nwin);
+}
+
 int check_gpu() {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -3138,8 +3156,8 @@ static int exec_topk_impl(SdbGpuCtx* ctx, SdbGpuSegment* const* segs,
     uint32_t wgs_per_cu = (uint32_t)(163840 / lds_bytes);
     if (wgs_per_cu < 1) wgs_per_cu = 1;
     if (wgs_per_cu > 4) wgs_per_cu = 4;
-    uint32_t ngrid = 256u * wgs_per_cu;
-    if (ngrid > nwin) ngrid = nwin;
+    const uint32_t ngrid = window_grid(wgs_per_cu, nwin);
+    ctx->last_window_grid = ngrid;
     if (wide_span)
       hipLaunchKernelGGL(topk_window_kernel<true>, dim3(ngrid),
                          dim3(SDB_NTHREADS), lds_bytes, ctx->stream, a,
@@ -3480,8 +3498,8 @@ static int exec_topk_batch_impl(
                     sizeof(SdbBlockDesc) * gen_dcache_n * plan->nterms));
       if (wgs_per_cu < 1) wgs_per_cu = 1;
       if (wgs_per_cu > 4) wgs_per_cu = 4;
-      uint32_t ngrid = 256u * wgs_per_cu;
-      if (ngrid > nwin) ngrid = nwin;
+      const uint32_t ngrid = window_grid(wgs_per_cu, nwin);
+      ctx->last_window_grid = ngrid;
       const size_t gen_lds =
         lds_fixed_gen + sizeof(SdbBlockDesc) * gen_dcache_n * plan->nterms;
       if (wide_span)
@@ -3804,6 +3822,14 @@ int sdb_gpu_last_stats(SdbGpuCtx* ctx, double* kernel_ms, unsigned* ncand,
 int sdb_gpu_last_sweep_grid(SdbGpuCtx* ctx, unsigned* grid) {
   if (!ctx || !grid) return SDB_ERR_INVALID;
   *grid = ctx->last_sweep_grid;
+  return SDB_OK;
+}
+
+// the same for the general window kernel (topk_window_kernel): what
+// SDB_WINDOW_GRID came to
+int sdb_gpu_last_window_grid(SdbGpuCtx* ctx, unsigned* grid) {
+  if (!ctx || !grid) return SDB_ERR_INVALID;
+  *grid = ctx->last_window_grid;
   return SDB_OK;
 }
 

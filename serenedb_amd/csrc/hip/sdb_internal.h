@@ -99,6 +99,7 @@ struct SdbGpuCtx {
   // breakdown of the last execute_topk (sdb_gpu_last_stats)
   unsigned last_ncand;
   unsigned last_sweep_grid;  // sdb_gpu_last_sweep_grid
+  unsigned last_window_grid; // sdb_gpu_last_window_grid
   float last_gtau;
   double last_readback_ms;
   double last_select_ms;
